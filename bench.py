@@ -4,8 +4,15 @@ read-long's output restored in HBM, then bwa-sr-1 .. bwa-sr-N with mask_shortcut
 bwa-sr-finish (bin/proovread:705-905, 2026-2047) -- over a synthetic workload of BASELINE.json
 configs[1] size per GPU; beside it the rate of one bwa-sr-1 task (value_task).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K correction runs and prints the result line (`value`,
+`ms_per_step` and the loop's own log).  --dump-outputs DIR then writes what the last timed run
+left (see dump_outputs).  --full adds everything else: `value_task` and the per-stage, roofline
+and phase figures of the bwa-sr-1 task phase, the digests that check that every run gives the
+same reads, the GPU-seeding check against the host path, the CPU baseline and the byte-for-byte
+parity check against it.
 
 One step = one correction run as proovread makes it (correct.run_tasks on correct.GpuStages, the
 loop's multi-GPU layout; SURVEY.md §8e exact-parity option): the long-read set back
@@ -26,7 +33,7 @@ to read-long's output (pr_lrset_restore, device to device), then per task
             across the ranks
 
 `value` = the corrected long-read bases of the whole job per second of the run.  `value_task`
-repeats bwa-sr-1 alone on the raw reads (the round-5 headline's scope, commit DRY).
+(--full) repeats bwa-sr-1 alone on the raw reads (the round-5 headline's scope, commit DRY).
 
 Every rank generates the SAME global dataset (one genome, one long-read set, one 50x short-read
 run in sequencer order -- unsorted over the genome): configs[1] x N (weak scaling: each rank owns
@@ -79,7 +86,13 @@ def parse():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--scale", type=float, default=1.0, help="fraction of the configs[1] workload per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed correction runs also the bwa-sr-1 task phase (value_task, stage, roofline "
+                         "and phase figures), the repeat digests, the seeding check, the CPU baseline and the parity "
+                         "check against it")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed correction run computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: neither CPU baseline nor parity check")
     ap.add_argument("--loop-only", action="store_true",
                     help="profiling: the correction runs only (no value_task phase, no CPU baseline)")
     ap.add_argument("--task-only", action="store_true",
@@ -89,7 +102,14 @@ def parse():
     ap.add_argument("--comm", choices=("rccl", "none"), default="rccl",
                     help="rccl: the step all-reduces the device {bpt, bpN} statistic over an RCCL communicator at "
                          "every world size (N=1 included, exactly as N>1 runs it); none: no communicator at N=1")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.task_only:
+        if args.dump_outputs:
+            ap.error("--task-only times no correction run: nothing for --dump-outputs to write")
+        args.full = True   # (the task phase is part of --full)
+    return args
 
 
 def host_cpu() -> str:
@@ -234,10 +254,13 @@ def main():
         h.update("".join(chim).encode())
         return h.hexdigest()
 
+    # the digests (a download and a hash of every read) check that the runs repeat: --full and
+    # --loop-only only
+    with_digest = args.full or args.loop_only
     first_digest = None
     for k in range(0 if args.task_only else args.warmup):
         chim, _ = loop_step()
-        if k == 0:
+        if k == 0 and with_digest:
             first_digest = digest(chim)
     if cm is not None:
         cm.barrier()
@@ -255,8 +278,10 @@ def main():
     _abi.check(L.pr_ctx_sync(ctx.h), "pr_ctx_sync")
     el = time.perf_counter() - t0
     loop_dev_ms = (stages.device_ms - dev0) / max(args.steps, 1)
-    last_digest = digest(chim) if not args.task_only else None
+    last_digest = digest(chim) if with_digest and not args.task_only else None
     n_chim = len(chim)
+    if args.dump_outputs and rank == 0:   # (the set is all-gathered: every rank holds all of it)
+        dump_outputs(Path(args.dump_outputs), lrs, chim)
     if cm is not None:
         el = cm.allreduce_floats([el], comm_mod.RED_MAX)[0]
         total_bases = cm.allreduce_ints([own_bases])[0]
@@ -281,6 +306,48 @@ def main():
                 "last_task_consensus_phases": stages.last_iteration.cns_phase_ms()
                 if os.environ.get("PRGPU_CNS_PROF") else None}),
                   file=_JSON_OUT, flush=True)
+        if cm is not None:
+            cm.close()
+        return
+    value = total_bases * args.steps / el / 1e6 if not args.task_only else None
+    step_ms = el / args.steps * 1e3 if not args.task_only else None
+    # the result line of a plain run; --full adds the task phase's and the checks' fields to it
+    out = {
+        "metric": "corrected long-read Mbases/sec per node",
+        "value": round(value, 3) if value is not None else None,
+        "unit": "Mbases/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(step_ms, 3) if step_ms is not None else None,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int32",
+        "full": args.full,
+        "data": "synthetic: iid genome, CLR-like long reads (15 % error), 50x 150 bp short reads in sequencer order, "
+                "sampled per task by SeqChunker's chunk rule; the same dataset on every rank",
+        "config": {
+            "workload": "configs[1] per GPU: 4.6 Mb genome, 13,800 x 10 kb long reads (30x, 15% error), "
+                        "50x 2x150 short reads; one whole sr-noccs correction run per step (read-long's output "
+                        "restored in HBM, bwa-sr-1..N with mask_shortcut_frac, bwa-sr-finish)",
+            "genome_bp": gl, "long_reads": n_lr, "long_read_bases": int(lr_off[-1]), "short_reads": n_sr,
+            "owned_long_reads": hi - lo, "mode": mode,
+            "parallelism": f"exact-parity layout x{world}: every rank indexes all {n_lr} long reads, seeds and aligns "
+                           f"1/{world} of each task's short-read sample, alignments all-to-all to the long reads' "
+                           f"owners over RCCL (pr_aln_exchange), corrected reads all-gathered (pr_lrset_commit)",
+        },
+        "loop": {"tasks": loop_rows, "device_ms": round(loop_dev_ms, 1), "chimera_lines": n_chim,
+                 "same_task_list_every_step": same_tasks,
+                 "repeat_identical": (first_digest == last_digest) if first_digest is not None else None,
+                 "final_reads_sha256": last_digest},
+        "comm": "rccl" if cm is not None else "none",
+        "gen_s": round(gen_s, 1),
+        "upload_s": round(upload_s, 2),
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), file=_JSON_OUT, flush=True)
         if cm is not None:
             cm.close()
         return
@@ -372,8 +439,6 @@ def main():
         if cm is not None:
             cm.close()
         return
-    value = total_bases * args.steps / el / 1e6 if not args.task_only else None
-    step_ms = el / args.steps * 1e3 if not args.task_only else None
     task_ms = el_task / args.steps * 1e3
     dom_ms /= K
     dom_tops = dom_cells * OPS_PER_CELL / (dom_ms * 1e-3) / 1e12
@@ -401,34 +466,7 @@ def main():
                       f"{pm.get('_build', 'build not recorded')}"
         except Exception:
             traffic = traffic_cns = traffic_ext = traffic_seed = None
-    out = {
-        "metric": "corrected long-read Mbases/sec per node",
-        "value": round(value, 3) if value is not None else None,
-        "unit": "Mbases/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(step_ms, 3) if step_ms is not None else None,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "int32",
-        "data": "synthetic: iid genome, CLR-like long reads (15 % error), 50x 150 bp short reads in sequencer order, "
-                "sampled per task by SeqChunker's chunk rule; the same dataset on every rank",
-        "config": {
-            "workload": "configs[1] per GPU: 4.6 Mb genome, 13,800 x 10 kb long reads (30x, 15% error), "
-                        "50x 2x150 short reads; one whole sr-noccs correction run per step (read-long's output "
-                        "restored in HBM, bwa-sr-1..N with mask_shortcut_frac, bwa-sr-finish)",
-            "genome_bp": gl, "long_reads": n_lr, "long_read_bases": int(lr_off[-1]), "short_reads": n_sr,
-            "owned_long_reads": hi - lo, "mode": mode,
-            "parallelism": f"exact-parity layout x{world}: every rank indexes all {n_lr} long reads, seeds and aligns "
-                           f"1/{world} of each task's short-read sample, alignments all-to-all to the long reads' "
-                           f"owners over RCCL (pr_aln_exchange), corrected reads all-gathered (pr_lrset_commit)",
-        },
-        "loop": {"tasks": loop_rows, "device_ms": round(loop_dev_ms, 1), "chimera_lines": n_chim,
-                 "same_task_list_every_step": same_tasks,
-                 "repeat_identical": (first_digest == last_digest) if first_digest is not None else None,
-                 "final_reads_sha256": last_digest},
+    out.update({
         "value_task": round(total_bases / (task_ms * 1e-3) / 1e6, 3),
         "task": {"name": "bwa-sr-1", "ms": round(task_ms, 3), "short_reads": n1, "short_read_shard": s1 - s0,
                  "seeds": n_seeds, "alignments_received": int(n_recv), "coverage_cap": params1.coverage,
@@ -474,13 +512,10 @@ def main():
         "roofline_bwa_rounds": bwa_rounds_roofline(bwa_ms, n_seeds, bwa_ext, int(na_rep.value), bwa_rounds),
         "cpu_baseline": cpu,
         "cpu_baseline_reference": reference_cpu(),
-        "comm": "rccl" if cm is not None else "none",
         "seed_parity_vs_host": seed_check,
-        "gen_s": round(gen_s, 1),
-        "upload_s": round(upload_s, 2),
         "reads_ok": ok,
         "parity": parity,
-    }
+    })
     print(json.dumps(out), file=_JSON_OUT, flush=True)
     if cm is not None:
         cm.close()
@@ -488,6 +523,49 @@ def main():
         raise SystemExit(f"bench: {parity['mismatches']} of {parity['checked_reads']} reads differ from the CPU chain")
     if first_digest is not None and first_digest != last_digest:
         raise SystemExit("bench: the correction run's output differs between steps")
+
+
+DUMP_SAMPLE_READS = 256      # reads written out whole (bases and qualities): ~11 MB a pool as float32
+DUMP_SAMPLE_SEED = 20261015
+DUMP_CHIMERA_BYTES = 1 << 20
+
+
+def dump_outputs(dest: Path, lrs, chim):
+    """--dump-outputs: what the last timed correction run handed back -- the corrected long-read
+    set (offsets, bases, qualities: correct.run_tasks leaves it resident, a caller downloads it)
+    and the finish task's chimera lines -- as DEST/<name>.npy, ~25 MB in all:
+
+      read_offsets     float64 [n+1]  start of every read in the pools
+      read_checksums   float64 [n,4]  per read: sum of its base bytes, the same weighted by
+                                      1 + (position in the read mod 251), then both for the
+                                      qualities (exact in float64: every read of the set counts)
+      sample_reads     float64 [s]    a fixed seeded sample of read numbers, ascending
+      sample_bases     float32        the sampled reads' base bytes, concatenated
+      sample_quals     float32        the sampled reads' quality bytes, concatenated
+      chimera_lines    float32        the bytes of the chimera lines joined by newlines (first 1 MiB)
+    """
+    off, sq, ql, _ = lrs.download(seq=True, qual=True)
+    off = np.asarray(off, np.int64)
+    n = len(off) - 1
+    sums = np.zeros((n, 4), np.float64)
+    for a in range(0, n, 1024):   # (blocks of reads: the weights of a whole pool would take GBs)
+        b = min(a + 1024, n)
+        lo, hi = int(off[a]), int(off[b])
+        w = np.arange(hi - lo, dtype=np.int64) - np.repeat(off[a:b] - lo, np.diff(off[a:b + 1]))
+        w = w % 251 + 1
+        for c, pool in ((0, sq), (2, ql)):
+            v = pool[lo:hi].astype(np.int64)
+            for k, x in ((c, v), (c + 1, v * w)):
+                run = np.concatenate(([0], np.cumsum(x)))
+                sums[a:b, k] = run[off[a + 1:b + 1] - lo] - run[off[a:b] - lo]
+    pick = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, min(n, DUMP_SAMPLE_READS), replace=False))
+    take = np.concatenate([np.arange(off[i], off[i + 1]) for i in pick]) if len(pick) else np.zeros(0, np.int64)
+    text = np.frombuffer("\n".join(chim).encode()[:DUMP_CHIMERA_BYTES], np.uint8)
+    dest.mkdir(parents=True, exist_ok=True)
+    for name, arr in (("read_offsets", off.astype(np.float64)), ("read_checksums", sums),
+                      ("sample_reads", pick.astype(np.float64)), ("sample_bases", sq[take].astype(np.float32)),
+                      ("sample_quals", ql[take].astype(np.float32)), ("chimera_lines", text.astype(np.float32))):
+        np.save(dest / f"{name}.npy", arr)
 
 
 def lrs_index_ms(L, ctx) -> float:
