@@ -443,6 +443,10 @@ int pr_seed_gpu_seed_count(pr_ctx *ctx, int64_t *n);
 /* reads of the last pr_seed_gpu_map that outgrew pass 1's small scratch slices (64 reads per
  * wave, lane per read) and ran in pass 2 (one wave per read, the large slices) */
 int pr_seed_gpu_pass2_reads(pr_ctx *ctx, int64_t *n);
+/* reads the last pr_seed_gpu_map handed to each pass after the first, summed over its chunks:
+ * [pass 1b lane per read, pass 1b wave per read (many flagged reads: pass 1 again with the
+ * overflowed arrays grown), pass 2, the later passes (a read counts once per pass)] */
+int pr_seed_gpu_pass_reads(pr_ctx *ctx, int64_t *n4);
 /* milliseconds of the last pr_seed_gpu_map kernel (HIP events on the ctx stream) */
 int pr_seed_gpu_last_ms(pr_ctx *ctx, double *ms);
 /* Diagnostics: wall-clock ticks (100 MHz) of the last pr_seed_gpu_map summed over waves:

@@ -1,0 +1,189 @@
+// The library's private context (struct pr_ctx) and what the host files that share it need:
+// the error string, HIPCHK, device buffers and their ids, host <-> device copies.
+// Included by prgpu_api.cpp and seed_api.cpp; sw_api.cpp still goes through the ctx_* accessors.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/prgpu.h"
+#include "sw_dev.h"
+#include "seed_dev.h"
+
+using namespace prgpu;
+
+// sets pr_last_error's text (printf-style), returns `code` (prgpu_api.cpp)
+int set_error(int code, const char *fmt, ...);
+int pr_set_error(int code, const char *msg);
+#define HIPCHK(x)                                                                        \
+    do {                                                                                 \
+        hipError_t e_ = (x);                                                             \
+        if (e_ != hipSuccess)                                                            \
+            return set_error(PR_ERR_HIP, "%s failed: %s", #x, hipGetErrorString(e_));    \
+    } while (0)
+
+// device memory accounting behind pr_mem_stats (prgpu_api.cpp)
+void prgpu_mem_note(const char *grp, int id, int64_t delta);
+int prgpu_oom(const char *grp, int id, size_t want);
+
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    const char *grp = "buf";
+    int id = 0;
+    int ensure(size_t bytes) {
+        if (bytes <= cap && p) return 0;
+        release();
+        size_t want = bytes + 64;   // slack: kernels read whole dwords at the end of byte pools
+        if (hipMalloc(&p, want) != hipSuccess) {
+            p = nullptr;
+            return prgpu_oom(grp, id, want);
+        }
+        cap = want;
+        prgpu_mem_note(grp, id, (int64_t)want);
+        return 0;
+    }
+    void release() {
+        if (p) {
+            (void)hipFree(p);
+            prgpu_mem_note(grp, id, -(int64_t)cap);
+        }
+        p = nullptr;
+        cap = 0;
+    }
+    // grow to `bytes` keeping the first `used` bytes (stream-ordered copy, then synchronised)
+    int grow_keep(size_t bytes, size_t used, hipStream_t s) {
+        if (bytes <= cap && p) return 0;
+        void *np = nullptr;
+        const size_t want = bytes + bytes / 4 + 64;
+        if (hipMalloc(&np, want) != hipSuccess) return prgpu_oom(grp, id, want);
+        if (p && used) {
+            if (hipMemcpyAsync(np, p, used, hipMemcpyDeviceToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+                (void)hipFree(np);
+                return set_error(PR_ERR_HIP, "device copy failed (%s[%d] growth)", grp, id);
+            }
+        }
+        release();
+        p = np;
+        cap = want;
+        prgpu_mem_note(grp, id, (int64_t)want);
+        return 0;
+    }
+    template <class T>
+    T *as() const { return reinterpret_cast<T *>(p); }
+};
+
+enum CnsBufId {
+    CB_LR_OFF, CB_REF_SEQ, CB_REF_QUAL, CB_IGN_OFF, CB_IGN, CB_ALN_OFF, CB_POS, CB_SCORE, CB_AFLAGS,
+    CB_SEQ_OFF, CB_LSEQ, CB_CIG_OFF, CB_NCIG, CB_SEQ, CB_CIG,
+    CB_A_ST, CB_A_LEN, CB_A_NC, CB_A_BIN, CB_A_CB, CB_A_CE, CB_A_SB, CB_A_RPOS, CB_A_END,
+    CB_SORTED, CB_LST_SCORE, CB_LST_ALN, CB_KEPT, CB_BIN_OFF, CB_BIN_BASES, CB_WORK,
+    CB_OUT_OFF, CB_CHIM_OFF, CB_STATUS, CB_SEQ_LEN, CB_TRACE_LEN, CB_NCIGAR, CB_NCHIM,
+    CB_O_SEQ, CB_O_QUAL, CB_O_TRACE, CB_O_CIG, CB_O_CHIM, CB_PROF, CB_RETRY, CB_K,
+    CB_GSZS, CB_GSZC, CB_GSO, CB_GCO, CB_GTMP,
+    CB_COUNT
+};
+
+// masking buffers (pr_mask_run inputs / outputs, pr_iter_mask output and run lists)
+enum MaskBufId { MB_OFF, MB_SEQ, MB_QUAL, MB_OUT, MB_RUN_OFF, MB_RUNS, MB_TMP, MB_NRUNS, MB_ERR, MB_STATS, MB_COUNT };
+// device seeding: the index copy (SI_*) and per-call buffers (SB_*)
+enum SeedBufId {
+    SI_TEXT, SI_CSTART, SI_CBLK, SI_LROFF, SI_KOFF, SI_KPOS, SI_KEXT, SI_CNT0,
+    SB_SEQ = SI_CNT0 + 11, SB_OFF, SB_SCRATCH, SB_OUT, SB_NOUT, SB_STATUS, SB_NEXT, SB_PRE, SB_DENSE,
+    SX_LRSEQ, SX_KEY0, SX_KEY1, SX_VAL0, SX_KC, SX_CNTPTR, SX_TEMP, SI_KSPLIT, SX_VAL1, SX_KCC, SX_KOFFC, SX_KCUR,
+    SB_DP, SI_TEXT4, SB_ORDER, SI_BLKFR, SD_COUNT
+};
+// the exact-parity layout's exchange (pr_aln_exchange, owned batches): bounds, sort keys and
+// indices, counts, op prefix, send / receive records and CIGAR ops, grouped hand-off inputs,
+// the task's short reads
+// the resident long-read set: pools, the dense offsets of a commit, the commit's staging pools
+// (LS_RSEQ / LS_RQUAL: pr_lrset_snapshot's raw reads; LS_SRSAMP: pr_srset_sample's task sample)
+enum LrSetBufId {
+    LS_SEQ, LS_QUAL, LS_MAP, LS_OFF, LS_TSEQ, LS_TQUAL, LS_TMAP, LS_SRSEQ, LS_GSEQ, LS_GQUAL, LS_GMAP, LS_RSEQ, LS_RQUAL,
+    LS_SRSAMP, LS_COUNT
+};
+enum XchgBufId {
+    XB_BOUNDS, XB_KEY0, XB_KEY1, XB_IDX0, XB_IDX1, XB_CNT, XB_OPIN, XB_OPAT, XB_SREC, XB_SCIG, XB_TEMP,
+    XB_RREC, XB_RCIG, XB_RCIGAT, XB_GCNT, XB_GCNT64, XB_TASKOFF, XB_ERR, XB_GSR, XB_GSTATUS, XB_GPOS, XB_GSCORE,
+    XB_GNCIG, XB_GCIGAT, XB_GSTRAND, XB_GPASS, XB_SR, XB_SROFF, XB_COUNT
+};
+
+struct pr_ctx {
+    int device = 0;
+    int n_cu = 256;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[11] = {};   // 0-7: SW, consensus, pipeline; 8-10: seeding
+    // consensus resident batch
+    DevBuf cb[CB_COUNT];
+    bool cns_loaded = false;
+    int32_t n_lr = 0;
+    int64_t n_aln = 0, total_cols = 0, n_bins = 0, seq_cap = 0, chim_cap = 0;
+    int64_t seed_pass2 = 0;   // reads of the last pr_seed_gpu_map that needed the large slices
+    // reads the last pr_seed_gpu_map handed to pass 1b by lane, to pass 1b by wave, to pass 2 and
+    // to the grown slices of the later passes (counted per pass): pr_seed_gpu_pass_reads
+    int64_t seed_pass_reads[4] = {};
+    std::vector<int64_t> seed_pre;   // per-read prefix of the last pr_seed_gpu_map's seeds (SB_DENSE)
+    int64_t alg_bytes = 0;
+    int64_t k_need = 0;   // per-read bound of kept alignments (K pool slices)
+    bool has_ref = false, has_qual = false, has_ign = false;
+    std::vector<int64_t> out_off, chim_off, bin_off, lr_off_host;
+    float last_ms = 0.f;
+    // SW -> consensus pipeline (pr_iter_*)
+    bool pipe = false;
+    bool pipe_ref_ascii = false;   // pr_iter_batch.ref_seq given: consensus reference in CB_REF_SEQ
+    int pipe_sort_cap = 0;
+    DevBuf pb[12];          // task_off, cnt, err, then the -b/-l filter: keep, sorted, bin, nc, len, lists
+    float ms_pipe = 0.f, ms_cns = 0.f;
+    // SW resident batch
+    SwResident sw;
+    // masking
+    DevBuf mb[MB_COUNT];
+    // seeding
+    DevBuf sd[SD_COUNT];
+    bool seed_loaded = false;
+    seedc::IndexView seed_view{};
+    float ms_seed = 0.f, ms_seed_pass2 = 0.f;
+    float ms_index = 0.f;
+    int64_t seed_n_text = 0, seed_n_hits = 0;
+    int64_t seed_sr_bases = -1;   // bases of the short reads of the last pr_seed_gpu_map (SB_SEQ)
+    bool iter_masked = false;
+    bool cns_launched = false;   // a consensus launch filled the CB_O_* outputs
+    bool cns_gathered = false;   // the hand-off's SEQ / CIGAR offsets point into CB_SEQ / CB_CIG
+    // exact-parity layout: received alignments (pr_aln_exchange) and an owned batch
+    DevBuf xb[XB_COUNT];
+    bool x_ready = false;        // XB_RREC / XB_RCIG hold the last exchange's records
+    bool x_pass = false;         // world 1: the exchange is the identity, the owned launch reads the SW output
+    int64_t x_nrecv = 0, x_nrcig = 0;
+    std::vector<int64_t> x_from;  // records of the last exchange by source rank
+    // the resident long-read set (pr_lrset_*): reads, qualities, mapping reference (masked reads)
+    DevBuf ls[LS_COUNT];
+    std::vector<int64_t> ls_off;
+    int32_t ls_n = -1;
+    bool ls_map_is_reads = true;
+    std::vector<int64_t> ss_off;   // the resident short reads (pr_srset_load): offsets on the host
+    std::vector<int64_t> ss_samp_off;   // pr_srset_sample's task sample (LS_SRSAMP), empty: none
+    std::vector<int64_t> ls_raw_off;    // pr_lrset_snapshot's offsets, empty: none
+    bool own = false;            // the resident iteration batch is an owned batch (pr_iter_upload_owned)
+    bool own_ref_nt4 = false;    // its consensus reference is the SW long-read pool's slice (nt4)
+    bool own_sr_resident = false;   // its short reads are the resident ones (LS_SRSEQ)
+    int32_t own_lr0 = 0;
+};
+
+template <class T>
+static int upload(DevBuf &d, const T *h, size_t n, hipStream_t s) {
+    int rc = d.ensure(n * sizeof(T));
+    if (rc) return rc;
+    if (n && h) HIPCHK(hipMemcpyAsync(d.p, h, n * sizeof(T), hipMemcpyHostToDevice, s));
+    return 0;
+}
+
+template <class T>
+static int download(T *h, const DevBuf &d, size_t n, hipStream_t s, size_t first = 0) {   // elements [first, first + n)
+    if (h && n) HIPCHK(hipMemcpyAsync(h, d.as<T>() + first, n * sizeof(T), hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
+// the seed index built in HBM (seed_api.cpp); lr_dev: lr_seq is a device pointer (pr_lrset_index)
+int index_build(pr_ctx *c, const uint8_t *lr_seq, const int64_t *lr_off, int n_lr, bool lr_dev);

@@ -13,16 +13,12 @@
 #include <string>
 #include <vector>
 
-#include "../../include/prgpu.h"
+#include "ctx.h"
 #include "cns_dev.h"
-#include "sw_dev.h"
 #include "pipe_dev.h"
 #include "mask_dev.h"
-#include "seed_dev.h"
-#include "seed_index_dev.h"
 #include "xchg_dev.h"
 
-using namespace prgpu;
 int sw_get_ptrs(pr_ctx *c, SwPtrs *p);
 int sw_xchg_send(pr_ctx *c, XchgSend *X);
 pr_ctx *comm_ctx(pr_comm *c);
@@ -31,7 +27,7 @@ int sw_upload_device_seeds(pr_ctx *c, const pr_sw_batch *b, const pr_seed_task *
                            const uint8_t *dev_sr = nullptr, const uint8_t *dev_lr = nullptr);
 
 static thread_local std::string g_err;
-static int set_error(int code, const char *fmt, ...) {
+int set_error(int code, const char *fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -40,12 +36,6 @@ static int set_error(int code, const char *fmt, ...) {
     g_err = buf;
     return code;
 }
-#define HIPCHK(x)                                                                        \
-    do {                                                                                 \
-        hipError_t e_ = (x);                                                             \
-        if (e_ != hipSuccess)                                                            \
-            return set_error(PR_ERR_HIP, "%s failed: %s", #x, hipGetErrorString(e_));    \
-    } while (0)
 
 extern "C" const char *pr_last_error(void) { return g_err.c_str(); }
 extern "C" const char *pr_version(void) { return "prgpu 0.1.0 (gfx950)"; }
@@ -123,148 +113,6 @@ int prgpu_oom(const char *grp, int id, size_t want) {
     return set_error(PR_ERR_HIP, "hipMalloc(%zu) failed (%s[%d]; the library holds %.2f GB, device free %.2f of %.2f GB)",
                      want, grp, id, g_dev_bytes.load() / 1e9, fr / 1e9, total / 1e9);
 }
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    const char *grp = "buf";
-    int id = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap && p) return 0;
-        release();
-        size_t want = bytes + 64;   // slack: kernels read whole dwords at the end of byte pools
-        if (hipMalloc(&p, want) != hipSuccess) {
-            p = nullptr;
-            return prgpu_oom(grp, id, want);
-        }
-        cap = want;
-        prgpu_mem_note(grp, id, (int64_t)want);
-        return 0;
-    }
-    void release() {
-        if (p) {
-            (void)hipFree(p);
-            prgpu_mem_note(grp, id, -(int64_t)cap);
-        }
-        p = nullptr;
-        cap = 0;
-    }
-    // grow to `bytes` keeping the first `used` bytes (stream-ordered copy, then synchronised)
-    int grow_keep(size_t bytes, size_t used, hipStream_t s) {
-        if (bytes <= cap && p) return 0;
-        void *np = nullptr;
-        const size_t want = bytes + bytes / 4 + 64;
-        if (hipMalloc(&np, want) != hipSuccess) return prgpu_oom(grp, id, want);
-        if (p && used) {
-            if (hipMemcpyAsync(np, p, used, hipMemcpyDeviceToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-                (void)hipFree(np);
-                return set_error(PR_ERR_HIP, "device copy failed (%s[%d] growth)", grp, id);
-            }
-        }
-        release();
-        p = np;
-        cap = want;
-        prgpu_mem_note(grp, id, (int64_t)want);
-        return 0;
-    }
-    template <class T>
-    T *as() const { return reinterpret_cast<T *>(p); }
-};
-
-enum CnsBufId {
-    CB_LR_OFF, CB_REF_SEQ, CB_REF_QUAL, CB_IGN_OFF, CB_IGN, CB_ALN_OFF, CB_POS, CB_SCORE, CB_AFLAGS,
-    CB_SEQ_OFF, CB_LSEQ, CB_CIG_OFF, CB_NCIG, CB_SEQ, CB_CIG,
-    CB_A_ST, CB_A_LEN, CB_A_NC, CB_A_BIN, CB_A_CB, CB_A_CE, CB_A_SB, CB_A_RPOS, CB_A_END,
-    CB_SORTED, CB_LST_SCORE, CB_LST_ALN, CB_KEPT, CB_BIN_OFF, CB_BIN_BASES, CB_WORK,
-    CB_OUT_OFF, CB_CHIM_OFF, CB_STATUS, CB_SEQ_LEN, CB_TRACE_LEN, CB_NCIGAR, CB_NCHIM,
-    CB_O_SEQ, CB_O_QUAL, CB_O_TRACE, CB_O_CIG, CB_O_CHIM, CB_PROF, CB_RETRY, CB_K,
-    CB_GSZS, CB_GSZC, CB_GSO, CB_GCO, CB_GTMP,
-    CB_COUNT
-};
-
-// masking buffers (pr_mask_run inputs / outputs, pr_iter_mask output and run lists)
-enum MaskBufId { MB_OFF, MB_SEQ, MB_QUAL, MB_OUT, MB_RUN_OFF, MB_RUNS, MB_TMP, MB_NRUNS, MB_ERR, MB_STATS, MB_COUNT };
-// device seeding: the index copy (SI_*) and per-call buffers (SB_*)
-enum SeedBufId {
-    SI_TEXT, SI_CSTART, SI_CBLK, SI_LROFF, SI_KOFF, SI_KPOS, SI_KEXT, SI_CNT0,
-    SB_SEQ = SI_CNT0 + 11, SB_OFF, SB_SCRATCH, SB_OUT, SB_NOUT, SB_STATUS, SB_NEXT, SB_PRE, SB_DENSE,
-    SX_LRSEQ, SX_KEY0, SX_KEY1, SX_VAL0, SX_KC, SX_CNTPTR, SX_TEMP, SI_KSPLIT, SX_VAL1, SX_KCC, SX_KOFFC, SX_KCUR,
-    SB_DP, SI_TEXT4, SB_ORDER, SI_BLKFR, SD_COUNT
-};
-// the exact-parity layout's exchange (pr_aln_exchange, owned batches): bounds, sort keys and
-// indices, counts, op prefix, send / receive records and CIGAR ops, grouped hand-off inputs,
-// the task's short reads
-// the resident long-read set: pools, the dense offsets of a commit, the commit's staging pools
-// (LS_RSEQ / LS_RQUAL: pr_lrset_snapshot's raw reads; LS_SRSAMP: pr_srset_sample's task sample)
-enum LrSetBufId {
-    LS_SEQ, LS_QUAL, LS_MAP, LS_OFF, LS_TSEQ, LS_TQUAL, LS_TMAP, LS_SRSEQ, LS_GSEQ, LS_GQUAL, LS_GMAP, LS_RSEQ, LS_RQUAL,
-    LS_SRSAMP, LS_COUNT
-};
-enum XchgBufId {
-    XB_BOUNDS, XB_KEY0, XB_KEY1, XB_IDX0, XB_IDX1, XB_CNT, XB_OPIN, XB_OPAT, XB_SREC, XB_SCIG, XB_TEMP,
-    XB_RREC, XB_RCIG, XB_RCIGAT, XB_GCNT, XB_GCNT64, XB_TASKOFF, XB_ERR, XB_GSR, XB_GSTATUS, XB_GPOS, XB_GSCORE,
-    XB_GNCIG, XB_GCIGAT, XB_GSTRAND, XB_GPASS, XB_SR, XB_SROFF, XB_COUNT
-};
-
-struct pr_ctx {
-    int device = 0;
-    int n_cu = 256;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[11] = {};   // 0-7: SW, consensus, pipeline; 8-10: seeding
-    // consensus resident batch
-    DevBuf cb[CB_COUNT];
-    bool cns_loaded = false;
-    int32_t n_lr = 0;
-    int64_t n_aln = 0, total_cols = 0, n_bins = 0, seq_cap = 0, chim_cap = 0;
-    int64_t seed_pass2 = 0;   // reads of the last pr_seed_gpu_map that needed the large slices
-    int64_t seed_pass3 = 0;   // ... and the grown slices of the later passes (counted per pass)
-    std::vector<int64_t> seed_pre;   // per-read prefix of the last pr_seed_gpu_map's seeds (SB_DENSE)
-    int64_t alg_bytes = 0;
-    int64_t k_need = 0;   // per-read bound of kept alignments (K pool slices)
-    bool has_ref = false, has_qual = false, has_ign = false;
-    std::vector<int64_t> out_off, chim_off, bin_off, lr_off_host;
-    float last_ms = 0.f;
-    // SW -> consensus pipeline (pr_iter_*)
-    bool pipe = false;
-    bool pipe_ref_ascii = false;   // pr_iter_batch.ref_seq given: consensus reference in CB_REF_SEQ
-    int pipe_sort_cap = 0;
-    DevBuf pb[12];          // task_off, cnt, err, then the -b/-l filter: keep, sorted, bin, nc, len, lists
-    float ms_pipe = 0.f, ms_cns = 0.f;
-    // SW resident batch
-    SwResident sw;
-    // masking
-    DevBuf mb[MB_COUNT];
-    // seeding
-    DevBuf sd[SD_COUNT];
-    bool seed_loaded = false;
-    seedc::IndexView seed_view{};
-    float ms_seed = 0.f, ms_seed_pass2 = 0.f;
-    float ms_index = 0.f;
-    int64_t seed_n_text = 0, seed_n_hits = 0;
-    int64_t seed_sr_bases = -1;   // bases of the short reads of the last pr_seed_gpu_map (SB_SEQ)
-    bool iter_masked = false;
-    bool cns_launched = false;   // a consensus launch filled the CB_O_* outputs
-    bool cns_gathered = false;   // the hand-off's SEQ / CIGAR offsets point into CB_SEQ / CB_CIG
-    // exact-parity layout: received alignments (pr_aln_exchange) and an owned batch
-    DevBuf xb[XB_COUNT];
-    bool x_ready = false;        // XB_RREC / XB_RCIG hold the last exchange's records
-    bool x_pass = false;         // world 1: the exchange is the identity, the owned launch reads the SW output
-    int64_t x_nrecv = 0, x_nrcig = 0;
-    std::vector<int64_t> x_from;  // records of the last exchange by source rank
-    // the resident long-read set (pr_lrset_*): reads, qualities, mapping reference (masked reads)
-    DevBuf ls[LS_COUNT];
-    std::vector<int64_t> ls_off;
-    int32_t ls_n = -1;
-    bool ls_map_is_reads = true;
-    std::vector<int64_t> ss_off;   // the resident short reads (pr_srset_load): offsets on the host
-    std::vector<int64_t> ss_samp_off;   // pr_srset_sample's task sample (LS_SRSAMP), empty: none
-    std::vector<int64_t> ls_raw_off;    // pr_lrset_snapshot's offsets, empty: none
-    bool seed_sr_staged = false;   // SB_SEQ already holds the reads of the next pr_seed_gpu_map
-    bool own = false;            // the resident iteration batch is an owned batch (pr_iter_upload_owned)
-    bool own_ref_nt4 = false;    // its consensus reference is the SW long-read pool's slice (nt4)
-    bool own_sr_resident = false;   // its short reads are the resident ones (LS_SRSEQ)
-    int32_t own_lr0 = 0;
-};
 
 extern "C" int pr_device_count(int *n) {
     int c = 0;
@@ -399,14 +247,6 @@ extern "C" int pr_cns_bounds_of(const pr_cns_batch *b, pr_cns_bounds *out) {
     cns_caps(b, oo, co, nullptr);
     out->seq_cap = oo.back();
     out->chim_cap = co.back();
-    return 0;
-}
-
-template <class T>
-static int upload(DevBuf &d, const T *h, size_t n, hipStream_t s) {
-    int rc = d.ensure(n * sizeof(T));
-    if (rc) return rc;
-    if (n && h) HIPCHK(hipMemcpyAsync(d.p, h, n * sizeof(T), hipMemcpyHostToDevice, s));
     return 0;
 }
 
@@ -673,12 +513,6 @@ extern "C" int pr_cns_launch(pr_ctx *c, const pr_cns_params *p) {
     if (e != 0) return set_error(PR_ERR_HIP, "cns kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     HIPCHK(hipEventRecord(c->ev[5], c->stream));
     c->cns_launched = true;
-    return 0;
-}
-
-template <class T>
-static int download(T *h, const DevBuf &d, size_t n, hipStream_t s, size_t first = 0) {   // elements [first, first + n)
-    if (h && n) HIPCHK(hipMemcpyAsync(h, d.as<T>() + first, n * sizeof(T), hipMemcpyDeviceToHost, s));
     return 0;
 }
 
@@ -1749,8 +1583,6 @@ extern "C" int pr_iter_mask_download(pr_ctx *c, uint8_t *masked) {
     return 0;
 }
 
-static int index_build(pr_ctx *c, const uint8_t *lr_seq, const int64_t *lr_off, int n_lr, bool lr_dev);
-
 // ---------------------------------------------------------------------------
 // the resident long-read set (include/prgpu.h pr_lrset_*): the loop's LR.fq and LR.masked.fa
 // between tasks, in HBM
@@ -1959,765 +1791,6 @@ extern "C" int pr_lrset_commit(pr_ctx *c, pr_comm *comm, int flags) {
     c->ls_off = off;
     if (with_mask) c->ls_map_is_reads = false;
     else c->ls_map_is_reads = true;   // the finish task: the reads are their own mapping reference
-    return 0;
-}
-
-// ---------------------------------------------------------------------------
-// seeding on the device (seed_kernels.hip over seed_core.h)
-// the index text 16 bases per word (IndexView.text4) for the occurrence table's match lengths
-static int seed_text4(pr_ctx *c, seedc::IndexView &v, hipStream_t s) {
-    int rc = c->sd[SI_TEXT4].ensure((size_t)ix_pack4_words(v.n_text) * 8);
-    if (rc) return rc;
-    const int e = ix_pack4_launch(v.text, v.n_text, c->sd[SI_TEXT4].as<uint64_t>(), s);
-    if (e) return set_error(PR_ERR_HIP, "text packing: %s", hipGetErrorString((hipError_t)e));
-    v.text4 = c->sd[SI_TEXT4].as<uint64_t>();
-    // dense indexes (> 64 hits per 12-mer on average: configs[2] / [3] at one rank's share): the
-    // by-wave pass walks 16 bases per text round trip (seed_wave_kernel<1>: no 5-word buffers,
-    // more waves resident), the others 64 (tools/ab_scale.sh: profiles/r06_walk_ab.txt)
-    v.walk_nw = v.n_text > ((int64_t)64 << 24) ? 1 : 4;
-    if (const char *w = getenv("PRGPU_SEED_WALK_NW"))   // tuning hook: 1 or 4
-        v.walk_nw = atoi(w) == 1 ? 1 : 4;
-    return 0;
-}
-
-// Per 2^CB_SHIFT text block: the contig at its start, the next two contig starts inside it and
-// the coordinate offsets of those contigs (fr = p + delta, seed_core.h text_to_fr), so the
-// seeding's hit pass computes a hit's bwa coordinate with one table load instead of the cblk ->
-// cstart -> lr_off chain.  cstart / off: host arrays of the index (off rebased to 0).
-static int upload_blk_fr(pr_ctx *c, seedc::IndexView &v, const int64_t *cstart, const int64_t *off, int n_lr,
-                         int64_t l_pac, int64_t n_text, hipStream_t s) {
-    const int64_t nb = (n_text >> seedc::CB_SHIFT) + 1;
-    const int nc = 2 * n_lr;
-    const int bs = 1 << seedc::CB_SHIFT;
-    auto delta = [&](int ci) -> int64_t {
-        if (ci < n_lr) return off[ci] - cstart[ci];
-        const int rid = 2 * n_lr - 1 - ci;   // the reverse half holds the long reads in reverse order
-        return 2 * l_pac - off[rid + 1] - cstart[ci];
-    };
-    std::vector<seedc::BlkFr> t((size_t)nb);
-    int ci = 0;
-    for (int64_t b = 0; b < nb; ++b) {
-        const int64_t b0 = b << seedc::CB_SHIFT, b1 = b0 + bs;
-        while (ci + 1 < nc && cstart[ci + 1] <= b0) ++ci;
-        seedc::BlkFr &e = t[(size_t)b];
-        e.c0 = ci;
-        e.d0 = nc ? delta(ci) : 0;
-        e.d1 = ci + 1 < nc ? delta(ci + 1) : 0;
-        e.bnd = ci + 1 < nc && cstart[ci + 1] < b1 ? (int32_t)(cstart[ci + 1] - b0) : bs;
-        e.bnd2 = ci + 2 < nc && cstart[ci + 2] < b1 ? (int32_t)(cstart[ci + 2] - b0) : bs;
-    }
-    int rc = c->sd[SI_BLKFR].ensure(t.size() * sizeof(seedc::BlkFr));
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(c->sd[SI_BLKFR].p, t.data(), t.size() * sizeof(seedc::BlkFr), hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));   // (t is a host temporary)
-    v.blkfr = c->sd[SI_BLKFR].as<seedc::BlkFr>();
-    return 0;
-}
-
-extern "C" int pr_seed_gpu_upload(pr_ctx *c, const pr_seed_index *h) {
-    if (!c || !h) return set_error(PR_ERR_ARG, "null arg");
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const seedc::IndexView hv = seed_index_view(h);
-    const SeedIndexSizes z = seed_index_sizes(h);
-    DevBuf *D = c->sd;
-    int rc;
-    if ((rc = upload(D[SI_TEXT], hv.text, (size_t)z.text, s)) || (rc = upload(D[SI_CSTART], hv.cstart, (size_t)z.cstart, s)) ||
-        (rc = upload(D[SI_CBLK], hv.cblk, (size_t)z.cblk, s)) || (rc = upload(D[SI_LROFF], hv.lr_off, (size_t)z.lr_off, s)) ||
-        (rc = upload(D[SI_KOFF], hv.koff, (size_t)z.koff, s)) || (rc = upload(D[SI_KPOS], hv.kpos, (size_t)z.kpos, s)) ||
-        (rc = upload(D[SI_KEXT], hv.kext, (size_t)z.kpos, s)) ||
-        (z.ksplit && (rc = upload(D[SI_KSPLIT], hv.ksplit, (size_t)z.ksplit, s))))
-        return rc;
-    seedc::IndexView v = hv;
-    for (int j = 0; j < seedc::KI - 1; ++j) {
-        if ((rc = upload(D[SI_CNT0 + j], hv.cnt[j], (size_t)z.cnt[j], s))) return rc;
-        v.cnt[j] = D[SI_CNT0 + j].as<uint32_t>();
-    }
-    v.text = D[SI_TEXT].as<uint8_t>();
-    v.cstart = D[SI_CSTART].as<int64_t>();
-    v.cblk = D[SI_CBLK].as<int32_t>();
-    v.lr_off = D[SI_LROFF].as<int64_t>();
-    v.koff = D[SI_KOFF].as<uint64_t>();
-    v.kpos = D[SI_KPOS].as<uint32_t>();
-    v.kext = D[SI_KEXT].as<uint64_t>();
-    v.ksplit = z.ksplit ? D[SI_KSPLIT].as<uint64_t>() : nullptr;
-    if ((rc = seed_text4(c, v, s))) return rc;
-    if ((rc = upload_blk_fr(c, v, hv.cstart, hv.lr_off, hv.n_lr, hv.l_pac, hv.n_text, s))) return rc;
-    HIPCHK(hipStreamSynchronize(s));
-    c->seed_view = v;
-    c->seed_loaded = true;
-    return 0;
-}
-
-// the seed index built in HBM (seed_index.hip): the tables of pr_seed_index_build
-// lr_dev: lr_seq is a device pointer (the resident long-read set), copied on the device
-extern "C" int pr_seed_gpu_index_build(pr_ctx *c, const uint8_t *lr_seq, const int64_t *lr_off, int n_lr) {
-    return index_build(c, lr_seq, lr_off, n_lr, false);
-}
-
-static int index_build(pr_ctx *c, const uint8_t *lr_seq, const int64_t *lr_off, int n_lr, bool lr_dev) {
-    if (!c || n_lr < 0 || (n_lr && (!lr_seq || !lr_off))) return set_error(PR_ERR_ARG, "null arg");
-    for (int i = 0; i < n_lr; ++i)
-        if (lr_off[i + 1] < lr_off[i]) return set_error(PR_ERR_ARG, "lr_off not monotone");
-    const int64_t l_pac = n_lr ? lr_off[n_lr] - lr_off[0] : 0;
-    if (2 * l_pac + 2 * (int64_t)n_lr > seedc::MAX_TEXT)
-        return set_error(PR_ERR_CAPACITY, "long reads beyond the index's 2^33 text positions (l_pac < 4.29 Gb)");
-    if ((int64_t)n_lr >= ((int64_t)1 << seedc::FR_RID_BITS))
-        return set_error(PR_ERR_CAPACITY, "more than 2^24 long reads in one index");
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    DevBuf *D = c->sd;
-    const int64_t n_text = 2 * l_pac + 2 * (int64_t)n_lr;
-    // small host tables: rebased read offsets, contig starts, 4 KB block -> contig
-    std::vector<int64_t> off((size_t)n_lr + 1, 0), cstart(2 * (size_t)n_lr, 0);
-    for (int i = 0; i <= n_lr; ++i) off[(size_t)i] = lr_off[i] - (n_lr ? lr_off[0] : 0);
-    for (int i = 0; i < n_lr; ++i) {
-        cstart[(size_t)i] = off[(size_t)i] + i;
-        cstart[2 * (size_t)n_lr - 1 - i] = l_pac + n_lr + (l_pac - off[(size_t)i + 1]) + (n_lr - 1 - i);
-    }
-    const int64_t nb = (n_text >> seedc::CB_SHIFT) + 1;
-    std::vector<int32_t> cblk((size_t)nb, 0);
-    {
-        int ci = 0;
-        const int nc = 2 * n_lr;
-        for (int64_t b = 0; b < nb; ++b) {
-            while (ci + 1 < nc && cstart[(size_t)ci + 1] <= (b << seedc::CB_SHIFT)) ++ci;
-            cblk[(size_t)b] = ci;
-        }
-    }
-    const size_t nt = (size_t)(n_text > 0 ? n_text : 1);
-    // sorts of up to 2^31 text positions when the device has room for their buffers (~16 bytes a
-    // position + rocPRIM's temporaries: configs[2]'s 2.1 G-position text in one sort, 293 -> 151
-    // ms), else 2^30 (a divisor of 2^32 either way; PRGPU_INDEX_CHUNK=k: 2^k, a test hook that
-    // sends small texts through the chunked build)
-    int64_t chunk = (int64_t)1 << 30;
-    if (n_text > chunk) {
-        size_t fr = 0, tot = 0;
-        (void)hipMemGetInfo(&fr, &tot);
-        (void)hipGetLastError();
-        const int64_t have = (int64_t)(D[SX_KEY0].cap + D[SX_KEY1].cap + D[SX_VAL0].cap + D[SX_VAL1].cap + D[SX_TEMP].cap);
-        // (room for the bigger sort buffers with 64 GB to spare for the rest of the task)
-        if ((int64_t)fr + have >= ((int64_t)1 << 31) * 20 + ((int64_t)64 << 30)) chunk = (int64_t)1 << 31;
-    }
-    if (const char *ch = getenv("PRGPU_INDEX_CHUNK")) {
-        const int k = atoi(ch);
-        if (k >= 16 && k <= 31) chunk = (int64_t)1 << k;
-    }
-    const bool chunked = n_text > chunk;
-    const size_t ns = (size_t)(chunked ? chunk : (int64_t)nt);   // sort scratch entries
-    const size_t temp = seed_index_temp_bytes((int64_t)ns);
-    const size_t nk1 = (size_t)seedc::NK + 1;
-    // hits <= 12-mer starts; kpos / kext sized by the text (the count is known after the build)
-    int rc;
-    if ((rc = upload(D[SX_LRSEQ], lr_dev ? nullptr : (n_lr ? lr_seq + lr_off[0] : lr_seq), (size_t)l_pac, s)) ||
-        (rc = upload(D[SI_LROFF], off.data(), off.size(), s)) || (rc = upload(D[SI_CSTART], cstart.data(), cstart.size(), s)) ||
-        (rc = upload(D[SI_CBLK], cblk.data(), cblk.size(), s)) || (rc = D[SI_TEXT].ensure(nt)) ||
-        (rc = D[SX_KEY0].ensure(ns * 4)) || (rc = D[SX_KEY1].ensure(ns * 4)) || (rc = D[SX_VAL0].ensure(ns * 4)) ||
-        (rc = D[SX_KC].ensure(nk1 * 4)) || (rc = D[SI_KOFF].ensure(nk1 * 8)) ||
-        (rc = D[SI_KPOS].ensure(nt * 4)) || (rc = D[SI_KEXT].ensure(nt * 8)) || (rc = D[SX_TEMP].ensure(temp)) ||
-        (rc = D[SX_CNTPTR].ensure(sizeof(uint32_t *) * (seedc::KI - 1))))
-        return rc;
-    if (chunked && ((rc = D[SX_VAL1].ensure(ns * 4)) || (rc = D[SX_KCC].ensure(nk1 * 4)) ||
-                    (rc = D[SX_KOFFC].ensure(nk1 * 4)) || (rc = D[SX_KCUR].ensure(nk1 * 8))))
-        return rc;
-    const bool paged = n_text > (int64_t)seedc::POS_PAGE;
-    if (paged && (rc = D[SI_KSPLIT].ensure(nk1 * 8))) return rc;
-    if (lr_dev && l_pac) HIPCHK(hipMemcpyAsync(D[SX_LRSEQ].p, lr_seq + lr_off[0], (size_t)l_pac, hipMemcpyDeviceToDevice, s));
-    SeedIndexBuild B{};
-    uint32_t *cptr[seedc::KI - 1];
-    for (int j = 1; j < seedc::KI; ++j) {
-        if ((rc = D[SI_CNT0 + j - 1].ensure(((size_t)1 << (2 * j)) * 4))) return rc;
-        cptr[j - 1] = B.cnt[j - 1] = D[SI_CNT0 + j - 1].as<uint32_t>();
-    }
-    HIPCHK(hipMemcpyAsync(D[SX_CNTPTR].p, cptr, sizeof cptr, hipMemcpyHostToDevice, s));
-    B.lr_seq = D[SX_LRSEQ].as<uint8_t>();
-    B.lr_off = D[SI_LROFF].as<int64_t>();
-    B.n_lr = n_lr;
-    B.l_pac = l_pac;
-    B.cstart = D[SI_CSTART].as<int64_t>();
-    B.n_text = n_text;
-    B.text = D[SI_TEXT].as<uint8_t>();
-    B.chunk = chunk;
-    B.key0 = D[SX_KEY0].as<uint32_t>();
-    B.key1 = D[SX_KEY1].as<uint32_t>();
-    B.val0 = D[SX_VAL0].as<uint32_t>();
-    B.val1 = chunked ? D[SX_VAL1].as<uint32_t>() : nullptr;
-    B.kc = D[SX_KC].as<uint32_t>();
-    B.koff = D[SI_KOFF].as<uint64_t>();
-    B.kcc = chunked ? D[SX_KCC].as<uint32_t>() : nullptr;
-    B.koffc = chunked ? D[SX_KOFFC].as<uint32_t>() : nullptr;
-    B.kcur = chunked ? D[SX_KCUR].as<uint64_t>() : nullptr;
-    B.kpos = D[SI_KPOS].as<uint32_t>();
-    B.kext = D[SI_KEXT].as<uint64_t>();
-    B.ksplit = paged ? D[SI_KSPLIT].as<uint64_t>() : nullptr;
-    B.cnt_dev = reinterpret_cast<uint32_t *const *>(D[SX_CNTPTR].p);
-    B.temp = D[SX_TEMP].p;
-    B.temp_bytes = temp;
-    HIPCHK(hipEventRecord(c->ev[8], s));
-    const int e = seed_index_device_build(B, s);
-    if (e) return set_error(PR_ERR_HIP, "seed index build: %s", hipGetErrorString((hipError_t)e));
-    HIPCHK(hipEventRecord(c->ev[9], s));
-    uint64_t nh = 0;
-    HIPCHK(hipMemcpyAsync(&nh, B.koff + seedc::NK, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, c->ev[8], c->ev[9]) == hipSuccess) c->ms_index = ms;
-    if (n_text > (int64_t)seedc::POS_PAGE) {
-        // a build beyond 2^32 positions (configs[3] ranks) gives its sort buffers back (4 x 4-8 GB +
-        // rocPRIM's temporaries): there a rank's device memory peaks near the card's 288 GiB later
-        // in the task (DESIGN.md current status); smaller texts keep them for the next task's
-        // build (no re-allocation inside a timed step)
-        for (int id : {(int)SX_KEY0, (int)SX_KEY1, (int)SX_VAL0, (int)SX_VAL1, (int)SX_TEMP}) D[id].release();
-    }
-    seedc::IndexView v{};
-    v.text = B.text;
-    v.n_text = n_text;
-    v.cstart = B.cstart;
-    v.n_contig = 2 * n_lr;
-    v.cblk = D[SI_CBLK].as<int32_t>();
-    v.lr_off = B.lr_off;
-    v.n_lr = n_lr;
-    v.l_pac = l_pac;
-    v.koff = B.koff;
-    v.kpos = B.kpos;
-    v.kext = B.kext;
-    v.ksplit = B.ksplit;
-    for (int j = 0; j < seedc::KI - 1; ++j) v.cnt[j] = B.cnt[j];
-    if ((rc = seed_text4(c, v, s))) return rc;
-    if ((rc = upload_blk_fr(c, v, cstart.data(), off.data(), n_lr, l_pac, n_text, s))) return rc;
-    c->seed_view = v;
-    c->seed_loaded = true;
-    c->seed_n_text = n_text;
-    c->seed_n_hits = nh;
-    return 0;
-}
-
-// the six digests of pr_seed_index_digest over the device index (test hook)
-extern "C" int pr_seed_gpu_index_digest(pr_ctx *c, uint64_t *out6) {
-    if (!c || !out6) return set_error(PR_ERR_ARG, "null arg");
-    if (!c->seed_loaded || !c->seed_n_text) return set_error(PR_ERR_ARG, "no device-built seed index");
-    HIPCHK(hipSetDevice(c->device));
-    const seedc::IndexView &v = c->seed_view;
-    const size_t nt = (size_t)c->seed_n_text, nh = (size_t)c->seed_n_hits, nk = (size_t)seedc::NK;
-    std::vector<uint8_t> text(nt);
-    std::vector<uint64_t> koff(nk + 1);
-    std::vector<uint32_t> kpos(nh), kc(nk);
-    std::vector<uint64_t> kext(nh);
-    std::vector<int64_t> cstart((size_t)v.n_contig), lro((size_t)v.n_lr + 1);
-    std::vector<int32_t> cblk((size_t)((c->seed_n_text >> seedc::CB_SHIFT) + 1));
-    std::vector<std::vector<uint32_t>> cnt(seedc::KI);
-    HIPCHK(hipMemcpy(text.data(), v.text, nt, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(koff.data(), v.koff, (nk + 1) * 8, hipMemcpyDeviceToHost));
-    if (nh) HIPCHK(hipMemcpy(kpos.data(), v.kpos, nh * 4, hipMemcpyDeviceToHost));
-    if (nh) HIPCHK(hipMemcpy(kext.data(), v.kext, nh * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(kc.data(), c->sd[SX_KC].p, nk * 4, hipMemcpyDeviceToHost));
-    if (!cstart.empty()) HIPCHK(hipMemcpy(cstart.data(), v.cstart, cstart.size() * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(lro.data(), v.lr_off, lro.size() * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(cblk.data(), v.cblk, cblk.size() * 4, hipMemcpyDeviceToHost));
-    for (int j = 0; j < seedc::KI - 1; ++j) {
-        cnt[(size_t)j].resize((size_t)1 << (2 * (j + 1)));
-        HIPCHK(hipMemcpy(cnt[(size_t)j].data(), v.cnt[j], cnt[(size_t)j].size() * 4, hipMemcpyDeviceToHost));
-    }
-    cnt[seedc::KI - 1] = std::move(kc);
-    std::vector<uint64_t> ksplit(v.ksplit ? nk : 0);
-    if (v.ksplit) HIPCHK(hipMemcpy(ksplit.data(), v.ksplit, nk * 8, hipMemcpyDeviceToHost));
-    seed_digest_tables(text, koff, kpos, kext, cnt, cstart, cblk, lro, ksplit, out6);
-    return 0;
-}
-
-extern "C" int pr_seed_gpu_index_koff(pr_ctx *c, uint64_t *koff, uint64_t *ksplit) {
-    if (!c || !koff) return set_error(PR_ERR_ARG, "null arg");
-    if (!c->seed_loaded) return set_error(PR_ERR_ARG, "no device seed index");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(koff, c->seed_view.koff, ((size_t)seedc::NK + 1) * 8, hipMemcpyDeviceToHost));
-    if (ksplit && c->seed_view.ksplit)
-        HIPCHK(hipMemcpy(ksplit, c->seed_view.ksplit, (size_t)seedc::NK * 8, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-extern "C" int pr_seed_gpu_index_last_ms(pr_ctx *c, double *ms) {
-    if (!c || !ms) return set_error(PR_ERR_ARG, "null arg");
-    *ms = c->ms_index;
-    return 0;
-}
-
-// the resident short reads (include/prgpu.h pr_srset_load): the whole short-read input once;
-// a task's sample is gathered on the device from its record ranges
-extern "C" int pr_srset_load(pr_ctx *c, int64_t n_sr, const int64_t *off, const uint8_t *seq) {
-    if (!c || n_sr < 0 || !off || (off[n_sr] && !seq) || off[0] != 0) return set_error(PR_ERR_ARG, "bad arg");
-    HIPCHK(hipSetDevice(c->device));
-    int rc = upload(c->ls[LS_SRSEQ], seq, (size_t)off[n_sr], c->stream);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->ss_off.assign(off, off + n_sr + 1);
-    c->ss_samp_off.clear();
-    c->ls[LS_SRSAMP].release();
-    return 0;
-}
-
-extern "C" int pr_srset_sample(pr_ctx *c, const int64_t *ranges, int n_ranges) {
-    if (!c || n_ranges < 0 || (n_ranges && !ranges)) return set_error(PR_ERR_ARG, "null arg");
-    if (c->ss_off.empty()) return set_error(PR_ERR_ARG, "no resident short reads (pr_srset_load)");
-    const int64_t N = (int64_t)c->ss_off.size() - 1;
-    std::vector<int64_t> off(1, 0);
-    for (int k = 0; k < n_ranges; ++k) {
-        const int64_t r0 = ranges[2 * k], r1 = ranges[2 * k + 1];
-        if (r0 < 0 || r1 < r0 || r1 > N) return set_error(PR_ERR_ARG, "record range outside the short reads");
-        for (int64_t i = r0; i < r1; ++i) off.push_back(off.back() + c->ss_off[(size_t)i + 1] - c->ss_off[(size_t)i]);
-    }
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    int rc = c->ls[LS_SRSAMP].ensure((size_t)off.back() + 1);
-    if (rc) return rc;
-    int64_t at = 0;
-    for (int k = 0; k < n_ranges; ++k) {
-        const int64_t b0 = c->ss_off[(size_t)ranges[2 * k]], b1 = c->ss_off[(size_t)ranges[2 * k + 1]];
-        if (b1 > b0)
-            HIPCHK(hipMemcpyAsync(c->ls[LS_SRSAMP].as<uint8_t>() + at, c->ls[LS_SRSEQ].as<uint8_t>() + b0, (size_t)(b1 - b0),
-                                  hipMemcpyDeviceToDevice, s));
-        at += b1 - b0;
-    }
-    c->ss_samp_off.swap(off);
-    return 0;
-}
-
-extern "C" int pr_seed_gpu_map_sampled(pr_ctx *c, const pr_seed_opts *o, const int64_t *ranges, int n_ranges,
-                                       int32_t *status) {
-    if (!c || !o || n_ranges < 0 || (n_ranges && !ranges)) return set_error(PR_ERR_ARG, "null arg");
-    if (c->ss_off.empty()) return set_error(PR_ERR_ARG, "no resident short reads (pr_srset_load)");
-    const int64_t N = (int64_t)c->ss_off.size() - 1;
-    std::vector<int64_t> off(1, 0);
-    for (int k = 0; k < n_ranges; ++k) {
-        const int64_t r0 = ranges[2 * k], r1 = ranges[2 * k + 1];
-        if (r0 < 0 || r1 < r0 || r1 > N) return set_error(PR_ERR_ARG, "record range outside the short reads");
-        for (int64_t i = r0; i < r1; ++i) off.push_back(off.back() + c->ss_off[(size_t)i + 1] - c->ss_off[(size_t)i]);
-    }
-    const int64_t n = (int64_t)off.size() - 1;
-    if (n > INT32_MAX) return set_error(PR_ERR_CAPACITY, "too many short reads in one sample");
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    int rc = c->sd[SB_SEQ].ensure((size_t)off.back() + 1);
-    if (rc) return rc;
-    int64_t at = 0;
-    for (int k = 0; k < n_ranges; ++k) {
-        const int64_t b0 = c->ss_off[(size_t)ranges[2 * k]], b1 = c->ss_off[(size_t)ranges[2 * k + 1]];
-        if (b1 > b0)
-            HIPCHK(hipMemcpyAsync(c->sd[SB_SEQ].as<uint8_t>() + at, c->ls[LS_SRSEQ].as<uint8_t>() + b0, (size_t)(b1 - b0),
-                                  hipMemcpyDeviceToDevice, s));
-        at += b1 - b0;
-    }
-    c->seed_sr_staged = true;
-    return pr_seed_gpu_map(c, o, nullptr, off.data(), (int)n, nullptr, status);
-}
-
-extern "C" int pr_seed_gpu_map(pr_ctx *c, const pr_seed_opts *o, const uint8_t *sr_seq, const int64_t *sr_off, int n_sr,
-                               pr_seed_tasks *out, int32_t *status) {
-    if (!c) return set_error(PR_ERR_ARG, "null arg");
-    const bool staged = c->seed_sr_staged;   // pr_seed_gpu_map_sampled gathered the reads on the device
-    c->seed_sr_staged = false;
-    if (!o || n_sr < 0 || (n_sr && ((!sr_seq && !staged) || !sr_off))) return set_error(PR_ERR_ARG, "null arg");
-    pr_seed_tasks dummy;
-    const bool keep_on_device = out == nullptr;
-    if (!out) out = &dummy;
-    c->seed_pre.clear();
-    if (!c->seed_loaded) return set_error(PR_ERR_ARG, "no seed index on the device (pr_seed_gpu_upload)");
-    if (o->min_seed_len < seedc::KI) return set_error(PR_ERR_UNSUPPORTED, "min seed length below the 12-mer index");
-    if (o->max_occ <= 0 || o->w < 0) return set_error(PR_ERR_ARG, "bad seeding options");
-    out->n = 0;
-    out->t = nullptr;
-    if (n_sr && sr_off[0] != 0) return set_error(PR_ERR_ARG, "sr_off must start at 0");
-    for (int i = 0; i < n_sr; ++i)
-        if (sr_off[i + 1] < sr_off[i]) return set_error(PR_ERR_ARG, "sr_off not monotone");
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    DevBuf *D = c->sd;
-    int qmax = 1;
-    for (int i = 0; i < n_sr; ++i) qmax = std::max<int>(qmax, (int)(sr_off[i + 1] - sr_off[i]));
-    seedc::Caps caps = seedc::device_caps(qmax);
-    caps.hi = c->seed_view.ksplit != nullptr;   // text beyond 2^32: positions carry bit 32
-    caps.nopos = 1;   // the device tables keep the chaining's coordinates only (seed_core.h Caps)
-    // pass 1: 64 reads per wave, small slices sized for the batch; pass 2 (flagged reads): the
-    // large slices, one wave per read
-    seedc::Caps small = seedc::device_caps_small(std::min(qmax, caps.lmax));
-    small.hi = caps.hi;
-    small.nopos = 1;
-    // the finish tasks' near-exact mapping: pass 1's occurrence tables lazily, a start's hits on
-    // first use (seed_core.h materialize; the later passes build them eagerly, wave-parallel)
-    small.lazy = seedc::lazy_occ(*o) ? 1 : 0;
-    if (const char *sc = getenv("PRGPU_SEED_SMALL"))   // tuning hook: hits,iv,mems,seeds,chains
-        sscanf(sc, "%d,%d,%d,%d,%d", &small.hits, &small.iv, &small.mems, &small.seeds, &small.chains);
-    SeedDev K{};
-    K.V = c->seed_view;
-    K.O = *o;
-    K.n_sr = n_sr;
-    K.caps = small;
-    K.stride = seedc::scratch_bytes(small);
-    const char *wpc = getenv("PRGPU_SEED_WAVES_PER_CU");   // tuning hook
-    int64_t waves = (int64_t)c->n_cu * (wpc ? atoi(wpc) : 16);   // ~98 KB x 64 slices per wave at 150 bp
-    const int64_t nbatch = (n_sr + 63) / 64;
-    if (waves > nbatch) waves = nbatch;
-    if (waves < 1) waves = 1;
-    // PRGPU_SEED_BALANCE: every wave the same number of 64-read batches (fewer waves; measured
-    // slower at configs[1], 357 vs 345 ms: the lane phase wants every wave it can get)
-    if (getenv("PRGPU_SEED_BALANCE")) {
-        const int64_t rounds = (nbatch + waves - 1) / waves;
-        waves = (nbatch + rounds - 1) / rounds;
-    }
-    {   // pass 1's slices within a scratch budget: 15 % of the free device memory, between 24 and
-        // 40 GB (configs[1]'s 16 waves per CU need ~32 GB; long mr reads: fewer waves).  (Round 4
-        // capped it at 24 GB, which cut configs[1] to ~3,800 of its 4,096 waves.)
-        size_t fr = 0, tot = 0;
-        (void)hipMemGetInfo(&fr, &tot);
-        (void)hipGetLastError();
-        const int64_t have = (int64_t)D[SB_SCRATCH].cap;   // (already ours: counts as free)
-        const int64_t budget = std::min<int64_t>((int64_t)40 << 30,
-                                                 std::max<int64_t>((int64_t)24 << 30, ((int64_t)fr + have) * 15 / 100));
-        const int64_t wmax = std::max<int64_t>(c->n_cu, budget / (64 * K.stride));
-        if (waves > wmax) waves = wmax;
-    }
-    K.n_lanes = waves;
-    // mem_flt_chained_seeds' SW rows of pass 1 (reads >= 440 bp), lane-interleaved per wave
-    K.dp = nullptr;
-    if (seedc::seed_flt_min_score(*o, qmax) >= 0) {
-        int rc0 = D[SB_DP].ensure((size_t)waves * 2 * 201 * 64 * sizeof(int16_t));
-        if (rc0) return rc0;
-        K.dp = D[SB_DP].as<int16_t>();
-    }
-    int64_t lanes2 = (int64_t)c->n_cu * seed_slots_per_cu(c->seed_view.walk_nw);
-    const int64_t scratch = std::max<int64_t>(waves * 64 * K.stride, lanes2 * seedc::scratch_bytes(caps));
-    const int64_t nb = n_sr ? sr_off[n_sr] : 0;
-    // reads are mapped in chunks whose output slabs (caps.out seeds per read) fit a budget
-    // (PRGPU_SEED_OUT_MB, default 8 GB; configs[1]'s 460k reads are one chunk); every chunk's
-    // seeds are compacted into the dense list before the next chunk reuses the slab
-    const int64_t slot_bytes = (int64_t)caps.out * (int64_t)sizeof(pr_seed_task);
-    const char *ob = getenv("PRGPU_SEED_OUT_MB");
-    const int64_t out_budget = (ob ? std::max<int64_t>(1, atoll(ob)) : 8192) << 20;
-    const int64_t chunk = std::max<int64_t>(64, out_budget / slot_bytes / 64 * 64);
-    int rc;
-    c->seed_sr_bases = nb;
-    if ((!staged && (rc = upload(D[SB_SEQ], sr_seq, (size_t)nb, s))) || (rc = upload(D[SB_OFF], sr_off, (size_t)n_sr + 1, s)) ||
-        (rc = D[SB_SCRATCH].ensure((size_t)scratch)) ||
-        (rc = D[SB_OUT].ensure((size_t)(std::min<int64_t>(chunk, n_sr) * slot_bytes + 16))) ||
-        (rc = D[SB_NOUT].ensure((size_t)n_sr * 4 + 16)) || (rc = D[SB_STATUS].ensure((size_t)n_sr * 4 + 16)) ||
-        (rc = D[SB_NEXT].ensure(256)) || (rc = D[SB_PRE].ensure(((size_t)n_sr + 1) * 8)) ||
-        (rc = D[SB_DENSE].ensure(sizeof(pr_seed_task))))
-        return rc;
-    K.sr_seq = D[SB_SEQ].as<uint8_t>();
-    K.sr_off = D[SB_OFF].as<int64_t>();
-    K.out = D[SB_OUT].as<pr_seed_task>();
-    K.n_out = D[SB_NOUT].as<int32_t>();
-    K.status = D[SB_STATUS].as<int32_t>();
-    K.next = D[SB_NEXT].as<int32_t>();
-    K.prof = reinterpret_cast<unsigned long long *>(D[SB_NEXT].as<uint8_t>() + 64);
-    HIPCHK(hipMemsetAsync(K.next, 0, 256, s));
-    HIPCHK(hipEventRecord(c->ev[8], s));
-    c->seed_pass2 = 0;
-    c->seed_pass3 = 0;
-    std::vector<int32_t> nout((size_t)n_sr), st((size_t)n_sr);
-    std::vector<int64_t> pre((size_t)n_sr + 1, 0);
-    int64_t total = 0, bad = 0;
-    int32_t bad_flags = 0;
-    for (int64_t r0 = 0; r0 < n_sr; r0 += chunk) {
-        const int64_t r1 = std::min<int64_t>(n_sr, r0 + chunk);
-        K.caps = small;
-        K.stride = seedc::scratch_bytes(small);
-        K.n_lanes = waves;
-        K.scratch = D[SB_SCRATCH].as<uint8_t>();
-        K.rlist = nullptr;
-        K.n_list = 0;
-        K.out0 = r0;
-        K.n_sr = r1;
-        int32_t start = (int32_t)r0;
-        // PRGPU_SEED_LPT=1: the chunk's reads costliest first (seed_order_launch).  Measured at
-        // configs[1]: 312.5 against 306.2 ms in read order (the batches' lane phase grew more than
-        // the tail shrank), so read order stays the default
-        const char *lpt = getenv("PRGPU_SEED_LPT");
-        if (lpt && lpt[0] == '1') {
-            int32_t *order = nullptr;
-            if ((rc = D[SB_ORDER].ensure(seed_order_bytes(r1 - r0)))) return rc;
-            int eo = seed_order_launch(K, r0, r1 - r0, D[SB_ORDER].p, &order, (void *)s);
-            if (eo) return set_error(PR_ERR_HIP, "seed order: %s", hipGetErrorString((hipError_t)eo));
-            K.rlist = order;
-            K.n_list = r1 - r0;
-            start = 0;
-        }
-        HIPCHK(hipMemcpyAsync(K.next, &start, 4, hipMemcpyHostToDevice, s));
-        int e = seed_batch_launch(K, (void *)s);
-        if (e) return set_error(PR_ERR_HIP, "seed kernel: %s", hipGetErrorString((hipError_t)e));
-        if (r0 == 0) HIPCHK(hipEventRecord(c->ev[10], s));
-        std::vector<int32_t> st1((size_t)(r1 - r0)), no1((size_t)(r1 - r0));
-        if ((rc = download(st1.data(), D[SB_STATUS], (size_t)(r1 - r0), s, (size_t)r0)) ||
-            (rc = download(no1.data(), D[SB_NOUT], (size_t)(r1 - r0), s, (size_t)r0)))
-            return rc;
-        HIPCHK(hipStreamSynchronize(s));
-        std::vector<int32_t> redo;
-        // pass 2's slices; after the by-wave pass 1b they are that pass's (its leftovers overflowed
-        // them), so pass 2 is skipped and the later passes grow from them
-        seedc::Caps p2caps = caps;
-        bool p2_ran = false;
-        int32_t fl1 = 0;
-        int64_t need_hits = 0;   // the largest hit table a flagged read asked for
-        int64_t need_sum = 0, need_n = 0;   // (and their mean)
-        for (int64_t i = r0; i < r1; ++i)
-            if (st1[(size_t)(i - r0)]) {
-                redo.push_back((int32_t)i);
-                fl1 |= st1[(size_t)(i - r0)];
-                need_hits = std::max<int64_t>(need_hits, -(int64_t)no1[(size_t)(i - r0)]);
-                if (no1[(size_t)(i - r0)] < 0) need_sum -= no1[(size_t)(i - r0)], ++need_n;
-            }
-        // many flagged reads (the finish task maps to corrected reads at 30x long-read coverage:
-        // ~140 starts x 30 hits > 4096 for nearly every read): pass 1 again, lane per read, over
-        // them with the arrays that overflowed grown (within the scratch already allocated),
-        // instead of pass 2's one wave per read
-        if (redo.size() > 4096 && !(fl1 & (seedc::SC_OVER_LEN | seedc::SC_OVER_OUT))) {
-            seedc::Caps cb = small;
-            // the hit tables sized for the largest flagged read (dense indexes: configs[2] /
-            // configs[3], or N > 1 ranks of the exact layout, every read overflows pass 1)
-            if (fl1 & seedc::SC_OVER_HITS) {
-                // the largest flagged read's hit table (+ 1/8), not a multiple of pass 1's: the finish
-                // task's reads need just over pass 1's 4096 hits, and 4x slices cut the waves in flight
-                // (the occurrence table is latency-bound: 413 -> measured in DESIGN.md §5 round 6)
-                cb.hits = (int32_t)std::min<int64_t>(std::max<int64_t>((int64_t)cb.hits + 512, (need_hits + need_hits / 8 + 511) & ~(int64_t)511),
-                                                     (int64_t)1 << 20);
-                // their chaining never ran; random 12-mer hits become chains and seeds in
-                // proportion to the hits, so those arrays grow by the same factor
-                const int64_t f = std::min<int64_t>(16, std::max<int64_t>(1, cb.hits / small.hits));
-                cb.chains = (int32_t)(cb.chains * f);
-                cb.seeds = (int32_t)(cb.seeds * f);
-            }
-            if (fl1 & seedc::SC_OVER_IV) cb.iv *= 2;
-            if (fl1 & seedc::SC_OVER_MEMS) cb.mems *= 2;
-            if (fl1 & seedc::SC_OVER_SEEDS) cb.seeds *= 2;
-            if (fl1 & seedc::SC_OVER_CHAINS) cb.chains *= 2;
-            const int64_t sb = seedc::scratch_bytes(cb);
-            {   // room for as many waves as pass 1 ran (or the flagged reads' batches), within pass 1's budget
-                size_t fr = 0, tot = 0;
-                (void)hipMemGetInfo(&fr, &tot);
-                (void)hipGetLastError();
-                const int64_t have = (int64_t)D[SB_SCRATCH].cap;
-                const int64_t budget = std::min<int64_t>((int64_t)40 << 30,
-                                                         std::max<int64_t>((int64_t)24 << 30, ((int64_t)fr + have) * 15 / 100));
-                const int64_t want = std::min<int64_t>(waves, ((int64_t)redo.size() + 63) / 64) * 64 * sb;
-                if (want > have && want <= budget) {
-                    HIPCHK(hipStreamSynchronize(s));
-                    if ((rc = D[SB_SCRATCH].ensure((size_t)want))) return rc;
-                    K.scratch = D[SB_SCRATCH].as<uint8_t>();
-                }
-            }
-            int64_t wb = std::min<int64_t>((int64_t)D[SB_SCRATCH].cap / (64 * sb), ((int64_t)redo.size() + 63) / 64);
-            wb = std::min<int64_t>(wb, waves);   // (the filter rows' area holds `waves` waves)
-            // reads that need more than 4x pass 1's hits on average (dense indexes: configs[2] / [3]) one wave
-            // each (seed_wave_kernel: the chaining over the lanes) with pass 2's slices grown like
-            // cb: 64 such slices per wave fit only a few hundred waves in the scratch (a configs[3]
-            // rank's seeding 17.4 -> 4.1 s, configs[2] 1.01 -> 0.82 s).  The finish task's reads
-            // (just over pass 1's hits, ~30x coverage) stay lane per read (620 vs 724 ms as waves).
-            // PRGPU_SEED_1B=wave / lane forces either.
-            const char *p1b = getenv("PRGPU_SEED_1B");
-            const bool by_wave = p1b ? !strcmp(p1b, "wave") : need_sum > 4 * (int64_t)small.hits * need_n;
-            seedc::Caps cw = caps;
-            cw.hits = std::max(caps.hits, cb.hits);
-            cw.iv = std::max(caps.iv, cb.iv);
-            cw.mems = std::max(caps.mems, cb.mems);
-            cw.seeds = std::max(caps.seeds, cb.seeds);
-            cw.chains = std::max(caps.chains, cb.chains);
-            const int64_t sw = seedc::scratch_bytes(cw);
-            const int64_t ww = std::min<int64_t>(std::min<int64_t>(lanes2, (int64_t)redo.size()), (int64_t)D[SB_SCRATCH].cap / sw);
-            if (by_wave && ww >= c->n_cu) {
-                K.caps = cw;
-                K.stride = sw;
-                K.n_lanes = ww;
-                K.rlist = D[SB_PRE].as<int32_t>();
-                K.n_list = (int64_t)redo.size();
-                HIPCHK(hipMemcpyAsync(D[SB_PRE].p, redo.data(), redo.size() * 4, hipMemcpyHostToDevice, s));
-                HIPCHK(hipMemsetAsync(K.next, 0, 4, s));
-                e = seed_launch(K, (void *)s);
-                if (e) return set_error(PR_ERR_HIP, "seed kernel (pass 1b, waves): %s", hipGetErrorString((hipError_t)e));
-                p2caps = cw;
-                p2_ran = true;
-                std::vector<int32_t> st1b((size_t)(r1 - r0));
-                if ((rc = download(st1b.data(), D[SB_STATUS], (size_t)(r1 - r0), s, (size_t)r0))) return rc;
-                HIPCHK(hipStreamSynchronize(s));
-                std::vector<int32_t> left;
-                for (int32_t i : redo)
-                    if (st1b[(size_t)(i - r0)]) left.push_back(i);
-                redo.swap(left);
-                K.rlist = nullptr;
-                K.n_list = 0;
-            } else if (wb >= c->n_cu) {
-                K.caps = cb;
-                K.stride = sb;
-                K.n_lanes = wb;
-                K.rlist = D[SB_PRE].as<int32_t>();
-                K.n_list = (int64_t)redo.size();
-                HIPCHK(hipMemcpyAsync(D[SB_PRE].p, redo.data(), redo.size() * 4, hipMemcpyHostToDevice, s));
-                HIPCHK(hipMemsetAsync(K.next, 0, 4, s));
-                e = seed_batch_launch(K, (void *)s);
-                if (e) return set_error(PR_ERR_HIP, "seed kernel (pass 1b): %s", hipGetErrorString((hipError_t)e));
-                std::vector<int32_t> st1b((size_t)(r1 - r0));
-                if ((rc = download(st1b.data(), D[SB_STATUS], (size_t)(r1 - r0), s, (size_t)r0))) return rc;
-                HIPCHK(hipStreamSynchronize(s));
-                std::vector<int32_t> left;
-                for (int32_t i : redo)
-                    if (st1b[(size_t)(i - r0)]) left.push_back(i);
-                redo.swap(left);
-                K.rlist = nullptr;
-                K.n_list = 0;
-            }
-        }
-        c->seed_pass2 += (int64_t)redo.size();
-        if (!redo.empty()) {   // pass 2 over the flagged reads (rlist in SB_PRE)
-            K.rlist = D[SB_PRE].as<int32_t>();
-            if (!p2_ran) {
-                HIPCHK(hipMemcpyAsync(D[SB_PRE].p, redo.data(), redo.size() * 4, hipMemcpyHostToDevice, s));
-                HIPCHK(hipMemsetAsync(K.next, 0, 4, s));
-                K.caps = caps;
-                K.stride = seedc::scratch_bytes(caps);
-                K.n_lanes = std::min<int64_t>(lanes2, (int64_t)redo.size());
-                K.n_list = (int64_t)redo.size();
-                e = seed_launch(K, (void *)s);
-                if (e) return set_error(PR_ERR_HIP, "seed kernel (pass 2): %s", hipGetErrorString((hipError_t)e));
-                HIPCHK(hipStreamSynchronize(s));
-            }
-            // later passes: the reads that outgrew the large slices too (e.g. the finish task's
-            // near-exact reads at 30-60x long-read coverage: every 12-mer hits every copy, > 8192
-            // hits per read) again, with the arrays that overflowed grown, up to 4 times
-            seedc::Caps cg = p2caps;
-            for (int pass = 3; pass <= 6; ++pass) {
-                std::vector<int32_t> st2((size_t)(r1 - r0));
-                if ((rc = download(st2.data(), D[SB_STATUS], (size_t)(r1 - r0), s, (size_t)r0))) return rc;
-                HIPCHK(hipStreamSynchronize(s));
-                std::vector<int32_t> again;
-                int32_t fl = 0;
-                for (int32_t i : redo)
-                    if (st2[(size_t)(i - r0)]) again.push_back(i), fl |= st2[(size_t)(i - r0)];
-                if (again.empty() || (fl & (seedc::SC_OVER_LEN | seedc::SC_OVER_OUT))) break;
-                if (fl & seedc::SC_OVER_HITS) cg.hits *= 4;
-                if (fl & seedc::SC_OVER_IV) cg.iv *= 2;
-                if (fl & seedc::SC_OVER_MEMS) cg.mems *= 2;
-                if (fl & seedc::SC_OVER_SEEDS) cg.seeds *= 2;
-                if (fl & seedc::SC_OVER_CHAINS) cg.chains *= 2;
-                redo.swap(again);
-                K.caps = cg;
-                K.stride = seedc::scratch_bytes(cg);
-                K.n_lanes = std::min<int64_t>(lanes2, (int64_t)redo.size());
-                if ((rc = D[SB_SCRATCH].ensure((size_t)(K.n_lanes * K.stride)))) return rc;
-                K.scratch = D[SB_SCRATCH].as<uint8_t>();
-                K.n_list = (int64_t)redo.size();
-                HIPCHK(hipMemcpyAsync(D[SB_PRE].p, redo.data(), redo.size() * 4, hipMemcpyHostToDevice, s));
-                HIPCHK(hipMemsetAsync(K.next, 0, 4, s));
-                e = seed_launch(K, (void *)s);
-                if (e) return set_error(PR_ERR_HIP, "seed kernel (pass %d): %s", pass, hipGetErrorString((hipError_t)e));
-                HIPCHK(hipStreamSynchronize(s));
-                c->seed_pass3 += (int64_t)redo.size();
-            }
-        }
-        // the chunk's seeds: compacted on the device (read order) behind the earlier chunks'
-        if ((rc = download(nout.data() + r0, D[SB_NOUT], (size_t)(r1 - r0), s, (size_t)r0)) ||
-            (rc = download(st.data() + r0, D[SB_STATUS], (size_t)(r1 - r0), s, (size_t)r0)))
-            return rc;
-        HIPCHK(hipStreamSynchronize(s));
-        const int64_t t0 = total;
-        for (int64_t i = r0; i < r1; ++i) {
-            if (nout[(size_t)i] < 0 || nout[(size_t)i] > caps.out) return set_error(PR_ERR_HIP, "seed kernel: bad task count");
-            total += nout[(size_t)i];
-            pre[(size_t)i + 1] = total;
-            bad += st[(size_t)i] != 0;
-            bad_flags |= st[(size_t)i];
-        }
-        if ((rc = upload(D[SB_PRE], pre.data() + r0, (size_t)(r1 - r0 + 1), s)) ||
-            (rc = D[SB_DENSE].grow_keep(sizeof(pr_seed_task) * (size_t)(total > 0 ? total : 1),
-                                        sizeof(pr_seed_task) * (size_t)t0, s)))
-            return rc;
-        const int e2 = seed_compact_launch(D[SB_OUT].as<pr_seed_task>(), D[SB_NOUT].as<int32_t>() + r0,
-                                           D[SB_PRE].as<int64_t>(), r1 - r0, caps.out, D[SB_DENSE].as<pr_seed_task>(),
-                                           (void *)s);
-        if (e2) return set_error(PR_ERR_HIP, "seed compaction: %s", hipGetErrorString((hipError_t)e2));
-    }
-    HIPCHK(hipEventRecord(c->ev[9], s));
-    HIPCHK(hipStreamSynchronize(s));
-    float ms = 0.f;
-    if (n_sr && hipEventElapsedTime(&ms, c->ev[8], c->ev[9]) == hipSuccess) c->ms_seed = ms;
-    c->ms_seed_pass2 = 0.f;   // (the passes after the first chunk's pass 1; one chunk at configs[1])
-    if (n_sr && hipEventElapsedTime(&ms, c->ev[10], c->ev[9]) == hipSuccess) c->ms_seed_pass2 = ms;
-
-    // an incomplete seed set (flagged reads have no seeds) is never handed to
-    // pr_iter_upload_gpu_seeds: it refuses when seed_pre does not match the reads
-    if (bad) c->seed_pre.clear();
-    else c->seed_pre = pre;
-    if (keep_on_device) {   // the seeds stay in HBM for pr_iter_upload_gpu_seeds
-        HIPCHK(hipStreamSynchronize(s));
-        if (status) std::memcpy(status, st.data(), (size_t)n_sr * 4);
-        if (bad)
-            return set_error(PR_ERR_CAPACITY, "%lld reads outgrew the seeding scratch (status flags, or: 0x%x)",
-                             (long long)bad, bad_flags);
-        return 0;
-    }
-    out->t = (pr_seed_task *)std::malloc(sizeof(pr_seed_task) * (size_t)(total > 0 ? total : 1));
-    if (!out->t) return set_error(PR_ERR_ARG, "out of host memory");
-    if (total && (rc = download(out->t, D[SB_DENSE], (size_t)total, s))) return rc;
-    HIPCHK(hipStreamSynchronize(s));
-    out->n = total;
-    if (status) std::memcpy(status, st.data(), (size_t)n_sr * 4);
-    if (bad)
-        return set_error(PR_ERR_CAPACITY, "%lld reads outgrew the seeding scratch (status flags, or: 0x%x)", (long long)bad,
-                         bad_flags);
-    return 0;
-}
-
-extern "C" int pr_seed_gpu_seed_count(pr_ctx *c, int64_t *n) {
-    if (!c || !n) return set_error(PR_ERR_ARG, "null arg");
-    *n = c->seed_pre.empty() ? 0 : c->seed_pre.back();
-    return 0;
-}
-
-extern "C" int pr_seed_gpu_pass2_reads(pr_ctx *c, int64_t *n) {
-    if (!c || !n) return set_error(PR_ERR_ARG, "null arg");
-    *n = c->seed_pass2;
-    return 0;
-}
-
-extern "C" int pr_seed_gpu_last_ms(pr_ctx *c, double *ms) {
-    if (!c || !ms) return set_error(PR_ERR_ARG, "null arg");
-    *ms = c->ms_seed;
-    return 0;
-}
-
-extern "C" int pr_seed_gpu_pass2_ms(pr_ctx *c, double *ms) {
-    if (!c || !ms) return set_error(PR_ERR_ARG, "null arg");
-    *ms = c->ms_seed_pass2;   // from pass 1's end to pass 2's (its status download included)
-    return 0;
-}
-
-extern "C" int pr_seed_gpu_phase_ticks(pr_ctx *c, uint64_t *ticks4) {
-    if (!c || !ticks4) return set_error(PR_ERR_ARG, "null arg");
-    if (!c->sd[SB_NEXT].p) return set_error(PR_ERR_ARG, "no pr_seed_gpu_map launch yet");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpy(ticks4, c->sd[SB_NEXT].as<uint8_t>() + 64, 32, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-extern "C" int pr_seed_gpu_lane_ticks(pr_ctx *c, uint64_t *ticks6) {
-    if (!c || !ticks6) return set_error(PR_ERR_ARG, "null arg");
-    if (!c->sd[SB_NEXT].p) return set_error(PR_ERR_ARG, "no pr_seed_gpu_map launch yet");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpy(ticks6, c->sd[SB_NEXT].as<uint8_t>() + 64 + 4 * 8, 48, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-extern "C" int pr_seed_gpu_pass2_ticks(pr_ctx *c, uint64_t *t7) {
-    if (!c || !t7) return set_error(PR_ERR_ARG, "null arg");
-    if (!c->sd[SB_NEXT].p) return set_error(PR_ERR_ARG, "no pr_seed_gpu_map launch yet");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpy(t7, c->sd[SB_NEXT].as<uint8_t>() + 64 + 13 * 8, 56, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-extern "C" int pr_seed_gpu_occ_ticks(pr_ctx *c, uint64_t *ticks3) {
-    if (!c || !ticks3) return set_error(PR_ERR_ARG, "null arg");
-    if (!c->sd[SB_NEXT].p) return set_error(PR_ERR_ARG, "no pr_seed_gpu_map launch yet");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpy(ticks3, c->sd[SB_NEXT].as<uint8_t>() + 64 + 10 * 8, 24, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -773,11 +773,7 @@ extern "C" int pr_seed_map_device_caps(const pr_seed_index *h, const pr_seed_opt
             // the device's later passes: the arrays that overflowed grown, up to 4 times
             seedc::Caps cg = caps;
             for (int pass = 3; pass <= 6 && err && !(err & (seedc::SC_OVER_LEN | seedc::SC_OVER_OUT)); ++pass) {
-                if (err & seedc::SC_OVER_HITS) cg.hits *= 4;
-                if (err & seedc::SC_OVER_IV) cg.iv *= 2;
-                if (err & seedc::SC_OVER_MEMS) cg.mems *= 2;
-                if (err & seedc::SC_OVER_SEEDS) cg.seeds *= 2;
-                if (err & seedc::SC_OVER_CHAINS) cg.chains *= 2;
+                cg = seedc::grow_caps(cg, err, 4);
                 big.assign((size_t)(seedc::scratch_bytes(cg) / 8 + 1), fill);
                 seedc::Scratch G = seedc::carve(reinterpret_cast<uint8_t *>(big.data()), cg);
                 err = seedc::map_read(V, *o, G, sr_seq + sr_off[i], len, i, buf.data(), caps.out, &n);

@@ -1495,6 +1495,17 @@ SC_HD Caps device_caps_small(int lmax) {
     }
     return c;
 }
+// The one growth rule of the passes after the first: every array whose SC_OVER_* bit is in
+// `flags` grown, the hit table by `hits_factor` (4 in the later passes and the host emulation;
+// 1 in pass 1b, which sizes its hits from the largest need before), the others doubled.
+SC_HD Caps grow_caps(Caps c, int32_t flags, int32_t hits_factor) {
+    if (flags & SC_OVER_HITS) c.hits *= hits_factor;
+    if (flags & SC_OVER_IV) c.iv *= 2;
+    if (flags & SC_OVER_MEMS) c.mems *= 2;
+    if (flags & SC_OVER_SEEDS) c.seeds *= 2;
+    if (flags & SC_OVER_CHAINS) c.chains *= 2;
+    return c;
+}
 
 SC_HD int64_t align8(int64_t x) { return (x + 7) & ~(int64_t)7; }
 SC_HD int32_t range_table_size(int32_t chains) {

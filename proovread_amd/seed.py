@@ -203,6 +203,11 @@ def _phase_ms(L, ctx) -> dict:
     out = {k: round(float(v) / 1e5, 1) for k, v in
            zip(("occ_table", "lane_phase_and_pass2_smems", "pass2_chaining", "pass2_filter_out"), t)}
     out["pass2_reads"] = n2.value
+    if hasattr(L, "pr_seed_gpu_pass_reads"):
+        pr = np.zeros(4, np.int64)
+        L.pr_seed_gpu_pass_reads.argtypes = [C.c_void_p, C.c_void_p]
+        _abi.check(L.pr_seed_gpu_pass_reads(ctx.h, pr.ctypes.data), "pr_seed_gpu_pass_reads")
+        out["pass_reads"] = dict(zip(("pass1b_lane", "pass1b_wave", "pass2", "later"), (int(v) for v in pr)))
     lt = np.zeros(6, np.uint64)
     L.pr_seed_gpu_lane_ticks.argtypes = [C.c_void_p, C.c_void_p]
     _abi.check(L.pr_seed_gpu_lane_ticks(ctx.h, lt.ctypes.data), "pr_seed_gpu_lane_ticks")

@@ -277,3 +277,45 @@ def test_gpu_seeding_near_exact_matches_host_path():
         assert np.array_equal(got, want)
         assert len(want) > 10 * n
     ix.close()
+
+
+def _pass1b_case(monkeypatch, mode, sr_frac, n_reads):
+    """The near-exact setting at ~47x long-read coverage with the iteration options: nearly every
+    read outgrows pass 1's 4,096 hits (and nothing else), so pass 1b runs, forced to `mode`.
+    -> its seeds, the host path's, the status, the reads handed to each pass."""
+    from proovread_amd import _abi
+    d = synth.simulate(17, 150_000, 1400, 5000, 40.0, p_ins=0.002, p_del=0.002, p_sub=0.002, sr_frac=sr_frac)
+    n = min(n_reads, d.n_sr)
+    assert n == n_reads
+    ss, so_ = d.sr_seq[:d.sr_off[n]], d.sr_off[:n + 1]
+    ix = seed.SeedIndex(d.lr_seq, d.lr_off)
+    ix.to_gpu(_abi.default_context())
+    o = seed.default_opts(False)
+    want = ix.map(ss, so_, o, threads=8)
+    monkeypatch.setenv("PRGPU_SEED_1B", mode)
+    got, st = ix.map_gpu(ss, so_, o, allow_flagged=True)
+    reads = ix.phase_ms()["pass_reads"]
+    ix.close()
+    print(f"pass 1b {mode}: {n} reads, handed to the passes: {reads}, flagged at the end: {int((st != 0).sum())}")
+    return got, want, st, reads
+
+
+@pytest.mark.gpu
+def test_gpu_seeding_pass1b_by_wave(monkeypatch):
+    """Pass 1b, one wave per read (6,000 reads, 5,854 of them flagged by pass 1 in the host
+    emulation of its capacities): the host path's seeds exactly, no read left flagged."""
+    got, want, st, reads = _pass1b_case(monkeypatch, "wave", 0.2, 6000)
+    assert reads["pass1b_wave"] > 4096 and reads["pass1b_lane"] == 0
+    assert not st.any()
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.gpu
+def test_gpu_seeding_pass1b_by_lane(monkeypatch):
+    """Pass 1b, lane per read: it needs a wave of 64 flagged reads per CU (256 x 64 = 16,384), so
+    24,000 reads, ~23,400 of them flagged by pass 1: the host path's seeds exactly, no read left
+    flagged."""
+    got, want, st, reads = _pass1b_case(monkeypatch, "lane", 0.6, 24000)
+    assert reads["pass1b_lane"] >= 16384 and reads["pass1b_wave"] == 0
+    assert not st.any()
+    assert np.array_equal(got, want)

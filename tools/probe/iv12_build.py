@@ -40,7 +40,7 @@ if trace:
 core.write_text(s)
 flags = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-pthread", "-ffp-contract=off", "-fno-fast-math",
          "-Wno-unused-function", "-Wno-unused-variable", "-Wno-format"]
-mine = ["seed_kernels.hip", "seed.cpp", "prgpu_api.cpp", "seed_index.hip"]
+mine = ["seed_kernels.hip", "seed.cpp", "prgpu_api.cpp", "seed_api.cpp", "seed_index.hip"]
 objs = []
 for o in sorted((ROOT / "build" / "obj").glob("*.o")):
     src = o.name[:-2]
