@@ -718,6 +718,74 @@ void pr_bam_alns_free(pr_bam_alns *a);
 int pr_bam_index(const uint8_t *data, int64_t len, int n_threads, uint8_t **out, int64_t *out_len);
 void pr_buffer_free(void *p);
 
+/* ------------------------------------------------------------------ */
+/* siamaera (bin/siamaera; bin/proovread:923-933): reverse-complement self-alignments of a
+ * read and the trimming decided from them.  REPLACES the two `blastn -strand minus` calls per
+ * read (siamaera:490-534 blast, :538-579 reblast) with exact seeds (maximal runs of
+ * self-complementary cells, length >= word) extended by ksw_extend2 with identity counts;
+ * blastn's own heuristics are not restated (parity unpinned).  Reads are nt4
+ * codes (A C G T = 0..3, anything else 4), read r at seq[off[r] .. off[r+1]).           */
+typedef struct pr_siam_aligner {
+    int32_t a, b;          /* match, mismatch penalty (any N scores -1)           */
+    int32_t o, e;          /* gap open / extend (deletions and insertions alike)  */
+    int32_t w, zdrop;      /* band (<= 31), z-drop                                */
+    int32_t word;          /* minimum seed length (28)                            */
+} pr_siam_aligner;
+typedef struct pr_siam_params {          /* siamaera:123-134 */
+    int32_t seq_min_len;                 /* 150                                   */
+    int32_t term_ignore_len;             /* 10                                    */
+    int32_t trim;                        /* 5                                     */
+    int32_t filter_inconclusive;         /* 1                                     */
+    double aln_min_idy;                  /* 97.5; pass 2 keeps aln_min_idy - 2    */
+    pr_siam_aligner pass1, pass2;        /* blast() :503-516, reblast() :551-561  */
+} pr_siam_params;
+typedef struct pr_siam_hsp {             /* blastn -outfmt 6 columns, 1-based, sas > sae */
+    int32_t read, qas, qae, sas, sae, length, matches, score;
+} pr_siam_hsp;
+enum { PR_SIAM_KEEP = 0, PR_SIAM_TRIM = 1, PR_SIAM_DROP = 2 };
+enum {                                   /* per-read status: the read is written unchanged */
+    PR_SIAM_SEED_OVERFLOW = 1,           /* more than PR_SIAM_MAX_SEEDS seeds     */
+    PR_SIAM_HSP_OVERFLOW = 2,            /* more than PR_SIAM_MAX_HSPS alignments */
+    PR_SIAM_TOO_LONG = 4,                /* longer than PR_SIAM_MAX_LEN           */
+};
+#define PR_SIAM_MAX_SEEDS 1024
+#define PR_SIAM_MAX_HSPS 64
+#define PR_SIAM_MAX_LEN 131072
+typedef struct pr_siam_decision {        /* TRIM keeps [from, to) of the read     */
+    int32_t action, from, to;
+} pr_siam_decision;
+void pr_siam_params_default(pr_siam_params *p);
+/* One blastn call per read (siamaera:490-534 with p->pass1 / min_idy, :538-579 with p->pass2 /
+ * min_idy - 2): the kept alignments of every read in order of production, after the identity
+ * threshold and -culling_limit 1.  *hsps is library-owned (valid until the thread's next
+ * pr_siam_* call); status[n] gets the PR_SIAM_* flags.  The host form runs n_threads threads
+ * (<= 0: all cores), the device form one wave per read (siam_kernels.hip).             */
+int pr_siam_hsps_host(const pr_siam_aligner *al, double min_idy, const uint8_t *seq, const int64_t *off, int32_t n,
+                      int n_threads, const pr_siam_hsp **hsps, int64_t *n_hsps, int32_t *status);
+int pr_siam_hsps_gpu(pr_ctx *ctx, const pr_siam_aligner *al, double min_idy, const uint8_t *seq, const int64_t *off,
+                     int32_t n, const pr_siam_hsp **hsps, int64_t *n_hsps, int32_t *status);
+/* The per-read loop of siamaera:250-474 on alignment lists: the spurious-hit filter (:277-312),
+ * pass 2's list h2 in place of what is left when more than 2 remain and h2 is not empty
+ * (:314-317), the filter again (:320-355), then the 1- and 2-alignment rules (:358-442).
+ * *inconclusive: more than 2 alignments were left (:446-448).                            */
+int pr_siam_decide(const pr_siam_params *p, int32_t len, const pr_siam_hsp *h1, int32_t n1, const pr_siam_hsp *h2,
+                   int32_t n2, pr_siam_decision *out, int32_t *inconclusive);
+/* siamaera's main loop (:250-474) for a batch: pass 1, the filter, pass 2 for the reads that
+ * need it, the decision.  ctx NULL: host (n_threads).  summary[4] = reads scanned, trimmed,
+ * inconclusive, flagged (status != 0; written unchanged).                                  */
+int pr_siam_run(pr_ctx *ctx, const pr_siam_params *p, const uint8_t *seq, const int64_t *off, int32_t n,
+                int n_threads, pr_siam_decision *out, int32_t *status, int64_t *summary);
+/* device milliseconds (HIP events around the kernels) of the context's last pr_siam_* call */
+int pr_siam_last_ms(pr_ctx *ctx, double *ms);
+/* test hooks: the seeds (i, p, len) of one read in (len desc, i asc, p asc) order, at most cap
+ * (*n is the full count); one extension -> out[5] = score, qle, tle, matches, cols; a batch
+ * of extensions on the device, pair k = q[q_off[k]..q_off[k+1]) against t[t_off[k]..).   */
+int pr_siam_seeds_host(const uint8_t *seq, int32_t len, int32_t word, int32_t *out, int32_t cap, int32_t *n);
+int pr_siam_extend_host(const pr_siam_aligner *al, const uint8_t *q, int32_t qlen, const uint8_t *t, int32_t tlen,
+                        int32_t h0, int32_t *out);
+int pr_siam_extend_gpu(pr_ctx *ctx, const pr_siam_aligner *al, const uint8_t *q, const int64_t *q_off,
+                       const uint8_t *t, const int64_t *t_off, const int32_t *h0, int32_t n, int32_t *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -604,11 +604,14 @@ def run_tasks(stages, srs: ShortReads, tasks: List[str], cfg: LoopConfig, mode: 
 
 
 # ---------------------------------------------------------------------------- outputs
-def write_outputs(res: LoopResult, pre: str, min_length: int = 500, trim_win: str = "12,5") -> None:
-    """The files of bin/proovread:905-958 (without siamaera, which needs BLAST):
-    PRE.untrimmed.fq, PRE.chim.tsv (ChimeraToSeqFilter of the finish task's chimera lines),
-    PRE.trimmed.fq (SeqFilter --trim-win 12,5 --min-length 500 --substr PRE.chim.tsv,
-    proovread.cfg:152-155) and PRE.trimmed.fa; also PRE.ignored.tsv."""
+def write_outputs(res: LoopResult, pre: str, min_length: int = 500, trim_win: str = "12,5", siamaera: bool = False,
+                  siamaera_device: bool = True) -> Optional[dict]:
+    """The files of bin/proovread:905-958: PRE.untrimmed.fq, PRE.chim.tsv (ChimeraToSeqFilter
+    of the finish task's chimera lines), PRE.trimmed.fq (SeqFilter --trim-win 12,5
+    --min-length 500 --substr PRE.chim.tsv, proovread.cfg:152-155) and PRE.trimmed.fa; also
+    PRE.ignored.tsv.  siamaera: PRE.trimmed.fq is the SeqFilter output passed through the
+    siamaera stage (proovread.cfg:159, bin/proovread:923-933; siamaera.py) -- the
+    reference's default, off here unless asked for; returns the stage's summary."""
     import os
     from . import chimera_filter, seqfilter
     with open(pre + ".untrimmed.fq", "w") as f:
@@ -622,8 +625,15 @@ def write_outputs(res: LoopResult, pre: str, min_length: int = 500, trim_win: st
                         "--in", pre + ".untrimmed.fq", "--out", pre + ".trimmed.fq", "--phred-offset", "33"])
     if rc:
         raise RuntimeError("SeqFilter trimming failed")
+    summary = None
+    if siamaera:
+        from . import siamaera as sia
+        recs, summary = sia.filter_records(seqfilter.read_records(pre + ".trimmed.fq"), device=siamaera_device)
+        with open(pre + ".trimmed.fq", "wb") as f:
+            f.write(b"".join(seqfilter.format_record(r, False, 0) for r in recs))
     if os.path.getsize(pre + ".trimmed.fq"):   # proovread:947
         seqfilter.run(["--in", pre + ".trimmed.fq", "--out", pre + ".trimmed.fa", "--fasta", "--phred-offset", "33"])
+    return summary
 
 
 # ---------------------------------------------------------------------------- command line
@@ -645,6 +655,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--coverage", type=float, default=50.0)
     ap.add_argument("--no-sampling", action="store_true")
     ap.add_argument("-t", "--threads", type=int, default=0)
+    ap.add_argument("--siamaera", action="store_true",
+                    help="pass the trimmed reads through the siamaera stage (the reference's default)")
     a = ap.parse_args(argv)
     lrs = []
     for f in a.long_reads:
@@ -663,7 +675,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         stages = GpuStages()
     res = run(lrs, sr_data, cfg, stages=stages, comm=comm)
     if rank == 0:
-        write_outputs(res, a.pre)
+        summary = write_outputs(res, a.pre, siamaera=a.siamaera)
+        if summary is not None:
+            from . import siamaera as sia
+            print("[siamaera] " + sia.summary_text(summary, True), file=sys.stderr)
         for e in res.log:
             if e.masked_frac is not None:
                 print(f"{e.task}: {e.n_sr} short reads, masked {100 * e.masked_frac:.1f}% {e.shortcut}", file=sys.stderr)
