@@ -505,6 +505,18 @@ int pr_iter_download_range(pr_ctx *ctx, int32_t first, int32_t n, pr_cns_out *ou
 int pr_iter_bounds(pr_ctx *ctx, int32_t *n_lr, int64_t *n_task, pr_cns_bounds *bd);
 /* reported alignments of the last iteration: count, total CIGAR ops, total SEQ bytes (syncs) */
 int pr_iter_alignment_stats(pr_ctx *ctx, int64_t *n_aln, int64_t *sum_ncig, int64_t *sum_lseq);
+/* Diagnostics of the last pr_iter_launch's hand-off.  A long read of up to 16,384 alignments
+ * (counted before -T and -b/-l drop any) is sorted into coordinate order in LDS; a larger one, up
+ * to 2^20, as runs in LDS merged in HBM; beyond 2^20 pr_iter_upload / pr_iter_launch return
+ * PR_ERR_CAPACITY naming the read.  big_reads: reads that took the HBM path (from the host's
+ * plan, no device access when the other two are NULL); big_alns: their alignments after the
+ * filters; max_alns: the most alignments on one read after the filters (these two sync). */
+int pr_iter_handoff_stats(pr_ctx *ctx, int64_t *big_reads, int64_t *big_alns, int32_t *max_alns);
+/* Test hook: the hand-off order of long read lr, as each alignment's index among the read's
+ * tasks (explicit tasks: task_lr_off[lr] + index is the task; bwa mode: among the read's
+ * reported alignments in SAM order).  n: the read's alignments; task_idx (room for cap, or NULL
+ * to ask for n only) receives them.  Syncs. */
+int pr_iter_handoff_order(pr_ctx *ctx, int32_t lr, int32_t *task_idx, int64_t cap, int64_t *n);
 int pr_iter_last_timing(pr_ctx *ctx, double *ms_sw_extend, double *ms_sw_global, double *ms_assemble,
                         double *ms_consensus);
 /* The exact-parity multi-GPU layout, device-resident.  proovread maps every

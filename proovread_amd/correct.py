@@ -423,6 +423,7 @@ class GpuStages:
         # iteration launch (hand-off, consensus; waits for it); chimera lines or masking; commit
         self.last_part_ms = {k: round((b - a) * 1e3, 2) for k, a, b in
                              zip(("index", "seed_sw_exchange", "consensus_launch", "chim_or_mask", "commit"), tp, tp[1:])}
+        self.last_part_ms["big_reads"] = it.handoff_stats(counts=False).big_reads   # reads sorted through HBM
         self.last_iteration = it   # the task's consensus outputs stay readable (tests, drivers)
         return out
 

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/prgpu.h"
+#include "handoff_plan.h"
 #include "sw_dev.h"
 #include "seed_dev.h"
 
@@ -110,6 +111,8 @@ enum XchgBufId {
     XB_GNCIG, XB_GCIGAT, XB_GSTRAND, XB_GPASS, XB_SR, XB_SROFF, XB_COUNT
 };
 
+enum PipeBufId { PB_TASK_OFF, PB_CNT, PB_ERR, PB_ORDER = 10, PB_BIG_LR, PB_BIG_OFF, PB_KEY0, PB_KEY1, PB_COUNT };
+
 struct pr_ctx {
     int device = 0;
     int n_cu = 256;
@@ -134,7 +137,12 @@ struct pr_ctx {
     bool pipe = false;
     bool pipe_ref_ascii = false;   // pr_iter_batch.ref_seq given: consensus reference in CB_REF_SEQ
     int pipe_sort_cap = 0;
-    DevBuf pb[12];          // task_off, cnt, err, then the -b/-l filter: keep, sorted, bin, nc, len, lists
+    // task_off, cnt, err, then the -b/-l filter: keep, sorted, bin, nc, len, lists (3-9), the
+    // hand-off order (10), and the HBM sort of the big reads: their list, key offsets, key buffers
+    DevBuf pb[PB_COUNT];
+    handp::Plan ho;              // the hand-off's sort plan (explicit tasks: at upload; bwa mode: at launch)
+    bool ho_done = false;        // a hand-off ran on this batch (pr_iter_handoff_stats / _order)
+    std::vector<int32_t> own_cnt_host;   // owned batch: received alignments per long read
     float ms_pipe = 0.f, ms_cns = 0.f;
     // SW resident batch
     SwResident sw;

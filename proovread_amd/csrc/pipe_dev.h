@@ -34,9 +34,24 @@ struct PipeDev {
     int32_t *a_lseq;
     int64_t *a_cig_off;
     int32_t *a_ncig;
+    int32_t *a_task;         // [alignments] the task's index within its read (pr_iter_handoff_order)
 };
 
-int pipe_launch(const PipeDev &P, int grid, void *stream, int lds_sort);
+// long reads of more than handp::LDS_KEYS tasks (handoff_plan.h): their keys are sorted as runs
+// in LDS and merged in HBM (pipe_big.hip)
+struct PipeBig {
+    int n_big;
+    int passes;                  // merge passes
+    int max_runs;                // runs of the largest read
+    int64_t max_big;             // its tasks
+    const int32_t *lr;           // [n_big] the reads
+    const int64_t *off;          // [n_big+1] first key of each read in k0 / k1 (prefix of their task counts)
+    unsigned long long *k0, *k1; // key buffers (ping-pong), off[n_big] keys each
+};
+
+// big: null when no read takes the HBM path (nothing more is launched)
+int pipe_launch(const PipeDev &P, int grid, void *stream, int lds_sort, const PipeBig *big = nullptr);
+int pipe_big_launch(const PipeDev &P, const PipeBig &G, void *stream);
 // bwa-proovread -b/-l score binning (the filter runs before pipe_launch when P.keep is set)
 int pipe_binfilter_launch(const PipeDev &P, int bin_size, double bin_length, int max_bins, int grid, void *stream);
 // dense pools of the consensus (d0), its quality (d1) and masked copy (d2) from the capacity layout

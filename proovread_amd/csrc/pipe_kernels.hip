@@ -12,12 +12,14 @@
 //                       alignment arrays are written in that order.  SEQ is not
 //                       materialised: the consensus reads the short read (nt4)
 //                       through the reverse-complement flag, and the CIGAR in
-//                       place from the SW output.
+//                       place from the SW output.  Reads of more than 16,384
+//                       tasks (handoff_plan.h) are left to pipe_big.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <rocprim/device/device_scan.hpp>
 
+#include "handoff_plan.h"
 #include "pipe_dev.h"
 
 namespace prgpu {
@@ -69,6 +71,7 @@ __global__ void __launch_bounds__(PIPE_THREADS) pipe_sort_kernel(PipeDev P) {
     __shared__ int s_n;
     for (int lr = blockIdx.x; lr < P.n_lr; lr += gridDim.x) {
         const int64_t t0 = P.task_off[lr], t1 = P.task_off[lr + 1];
+        if (t1 - t0 > handp::LDS_KEYS) continue;   // the HBM path's (pipe_big.hip)
         const int nt = (int)(t1 - t0);
         const int cnt = P.cnt[lr];
         if (cnt > P.sort_cap) {   // cannot happen: sort_cap >= max tasks per read (host)
@@ -114,6 +117,7 @@ __global__ void __launch_bounds__(PIPE_THREADS) pipe_sort_kernel(PipeDev P) {
             P.a_lseq[g] = (int32_t)(P.sr_off[sid + 1] - P.sr_off[sid]);
             P.a_cig_off[g] = P.cig_at[t];
             P.a_ncig[g] = P.ncig[t];
+            P.a_task[g] = (int32_t)(t - t0);
         }
         __syncthreads();
     }
@@ -314,7 +318,7 @@ int lr_compact_launch(const int64_t *src_off, const int32_t *len, const int64_t 
     return (int)hipGetLastError();
 }
 
-int pipe_launch(const PipeDev &P, int grid, void *stream, int lds_sort) {
+int pipe_launch(const PipeDev &P, int grid, void *stream, int lds_sort, const PipeBig *big) {
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(pipe_count_kernel, dim3(grid), dim3(PIPE_THREADS), 0, s, P);
     hipError_t e = hipGetLastError();
@@ -324,7 +328,8 @@ int pipe_launch(const PipeDev &P, int grid, void *stream, int lds_sort) {
     e = hipFuncSetAttribute((const void *)pipe_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_sort);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(pipe_sort_kernel, dim3(grid), dim3(PIPE_THREADS), lds_sort, s, P);
-    return (int)hipGetLastError();
+    if ((e = hipGetLastError()) != hipSuccess || !big || big->n_big == 0) return (int)e;
+    return pipe_big_launch(P, *big, stream);
 }
 
 // ---------------------------------------------------------------------------

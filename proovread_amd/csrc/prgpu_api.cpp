@@ -139,7 +139,7 @@ extern "C" int pr_ctx_create(int device, pr_ctx **out) {
         for (int i = 0; i < n; ++i) b[i].grp = g, b[i].id = i;
     };
     tag(c->cb, CB_COUNT, "cns");
-    tag(c->pb, 12, "pipe");
+    tag(c->pb, PB_COUNT, "pipe");
     tag(c->mb, MB_COUNT, "mask");
     tag(c->sd, SD_COUNT, "seed");
     tag(c->xb, XB_COUNT, "xchg");
@@ -575,6 +575,13 @@ extern "C" int pr_cns_resident_stats(pr_ctx *c, int64_t *columns, int64_t *alg_b
     return 0;
 }
 
+// the hand-off takes up to handp::MAX_ALNS alignments per long read (what: "tasks" / "alignments")
+static int handoff_refused(const handp::Plan &ho, const char *what) {
+    if (ho.refused_lr < 0) return 0;
+    return set_error(PR_ERR_CAPACITY, "long read %d has %lld %s: more than 2^20 (the consensus kernel's alignment index)",
+                     ho.refused_lr, (long long)ho.refused_count, what);
+}
+
 // ---------------------------------------------------------------------------
 // one iteration on the device: SW -> assemble -> consensus (pr_iter_*)
 // dev_*: device sources in place of the batch's host pools (the resident long-read set and the
@@ -596,18 +603,21 @@ static int iter_upload(pr_ctx *c, const pr_iter_batch *b, bool gpu_seeds, const 
     const bool bwa = sb.t_chain != nullptr || gpu_seeds;   // seeds in, alignments grouped by long read on the device
     if (!bwa && (!b->task_lr_off || b->task_lr_off[0] != 0 || b->task_lr_off[n] != sb.n_task))
         return set_error(PR_ERR_ARG, "task_lr_off must partition the tasks");
-    int maxt = 1;
+    // the hand-off's sort plan from the tasks per long read (bwa mode: from the alignment counts, at launch)
+    std::vector<int64_t> per_lr(bwa ? 0 : (size_t)n);
     for (int i = 0; i < n && !bwa; ++i) {
         if (b->task_lr_off[i + 1] < b->task_lr_off[i]) return set_error(PR_ERR_ARG, "task_lr_off not monotone");
+        per_lr[(size_t)i] = b->task_lr_off[i + 1] - b->task_lr_off[i];
+    }
+    handp::Plan ho = handp::plan(per_lr.data(), (int64_t)per_lr.size());
+    int rc = handoff_refused(ho, "tasks");
+    if (rc) return rc;
+    for (int i = 0; i < n && !bwa; ++i)
         for (int64_t t = b->task_lr_off[i]; t < b->task_lr_off[i + 1]; ++t)
             if (sb.t_lr[t] != i) return set_error(PR_ERR_ARG, "tasks must be grouped by long read");
-        const int64_t k = b->task_lr_off[i + 1] - b->task_lr_off[i];
-        if (k > maxt) maxt = (int)k;
-    }
-    if (maxt > 16384) return set_error(PR_ERR_CAPACITY, "more than 16384 tasks on one long read");
-    int rc = gpu_seeds ? sw_upload_device_seeds(c, &sb, c->sd[SB_DENSE].as<pr_seed_task>(), c->seed_pre.data(),
-                                                dev_sr, dev_lr)
-                       : pr_sw_upload(c, &sb);
+    const int64_t maxt = ho.max_count > 1 ? ho.max_count : 1;
+    rc = gpu_seeds ? sw_upload_device_seeds(c, &sb, c->sd[SB_DENSE].as<pr_seed_task>(), c->seed_pre.data(), dev_sr, dev_lr)
+                   : pr_sw_upload(c, &sb);
     if (rc) return rc;
     c->x_ready = c->x_pass = false;   // a new SW batch: no exchange of it yet
     HIPCHK(hipSetDevice(c->device));
@@ -635,9 +645,9 @@ static int iter_upload(pr_ctx *c, const pr_iter_batch *b, bool gpu_seeds, const 
     c->chim_cap = c->chim_off[n];
     c->alg_bytes = 0;
     c->k_need = maxt;
-    int sc = 1;
-    while (sc < maxt) sc <<= 1;
-    c->pipe_sort_cap = sc;
+    c->pipe_sort_cap = ho.sort_cap;
+    c->ho = std::move(ho);
+    c->ho_done = false;
     DevBuf *B = c->cb;
     const size_t na1 = (size_t)sb.n_task + 1, n1 = (size_t)n + 1;
     if ((rc = upload(B[CB_LR_OFF], sb.lr_off, n1, s))) return rc;
@@ -953,6 +963,8 @@ extern "C" int pr_iter_upload_owned(pr_ctx *c, const pr_own_batch *b) {
     c->alg_bytes = 0;
     c->k_need = 1;
     c->pipe_sort_cap = 1;
+    c->ho = handp::Plan();
+    c->ho_done = false;
     DevBuf *B = c->cb;
     const size_t n1 = (size_t)n + 1;
     if ((rc = upload(B[CB_LR_OFF], c->lr_off_host.data(), n1, s))) return rc;
@@ -1097,7 +1109,8 @@ static int own_group(pr_ctx *c, SwPtrs *sp) {
     R.o_pass = B[XB_GPASS].as<uint8_t>();
     int e = xchg_group_launch(R, B[XB_TEMP].p, B[XB_TEMP].cap, (void *)s);
     if (e) return set_error(PR_ERR_HIP, "exchange regroup: %s", hipGetErrorString((hipError_t)e));
-    std::vector<int32_t> cnt((size_t)c->n_lr + 1, 0);
+    std::vector<int32_t> &cnt = c->own_cnt_host;
+    cnt.assign((size_t)c->n_lr + 1, 0);
     int32_t err = 0;
     if (c->n_lr) HIPCHK(hipMemcpyAsync(cnt.data(), R.cnt, (size_t)c->n_lr * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(&err, R.err, 4, hipMemcpyDeviceToHost, s));
@@ -1119,6 +1132,7 @@ static int own_group(pr_ctx *c, SwPtrs *sp) {
     sp->n_task = R.n;
     sp->task_off = R.task_off;
     sp->max_per_lr = mx;
+    sp->cnt_host = cnt.data();
     return 0;
 }
 
@@ -1135,12 +1149,11 @@ extern "C" int pr_iter_launch(pr_ctx *c, const pr_sw_opts *o, const pr_cns_param
         if ((rc = sw_get_pipe_ptrs(c, &sp, true))) return rc;
     }
     if (sp.task_off) {   // bwa mode: the reported alignments grouped by long read on the device
-        if (sp.max_per_lr > 16384)
-            return set_error(PR_ERR_CAPACITY, "more than 16384 alignments on one long read (%d)", sp.max_per_lr);
-        c->k_need = sp.max_per_lr > 1 ? sp.max_per_lr : 1;
-        int sc = 1;
-        while (sc < c->k_need) sc <<= 1;
-        c->pipe_sort_cap = sc;
+        // (the counts before the -b/-l filter: upper bounds of what the hand-off sorts)
+        c->ho = handp::plan(sp.cnt_host, (int64_t)c->n_lr);
+        if ((rc = handoff_refused(c->ho, "alignments"))) return rc;
+        c->k_need = c->ho.max_count > 1 ? c->ho.max_count : 1;
+        c->pipe_sort_cap = c->ho.sort_cap;
     }
     DevBuf *B = c->cb;
     PipeDev P;
@@ -1170,6 +1183,25 @@ extern "C" int pr_iter_launch(pr_ctx *c, const pr_sw_opts *o, const pr_cns_param
     P.cig = sp.cig;
     P.keep = nullptr;
     if (c->n_lr == 0) return 0;
+    if ((rc = c->pb[PB_ORDER].ensure(((size_t)c->n_aln + 1) * 4))) return rc;
+    P.a_task = c->pb[PB_ORDER].as<int32_t>();
+    PipeBig G;
+    std::memset(&G, 0, sizeof G);
+    const handp::Plan &ho = c->ho;
+    if (ho.n_big) {   // reads beyond the LDS sort: their list and the key buffers of the HBM path
+        if ((rc = upload(c->pb[PB_BIG_LR], ho.big_lr.data(), ho.big_lr.size(), c->stream)) ||
+            (rc = upload(c->pb[PB_BIG_OFF], ho.big_off.data(), ho.big_off.size(), c->stream)) ||
+            (rc = c->pb[PB_KEY0].ensure((size_t)ho.scratch_bytes / 2)) || (rc = c->pb[PB_KEY1].ensure((size_t)ho.scratch_bytes / 2)))
+            return rc;
+        G.n_big = (int)ho.n_big;
+        G.passes = ho.passes;
+        G.max_runs = ho.max_runs;
+        G.max_big = ho.max_big;
+        G.lr = c->pb[PB_BIG_LR].as<int32_t>();
+        G.off = c->pb[PB_BIG_OFF].as<int64_t>();
+        G.k0 = c->pb[PB_KEY0].as<unsigned long long>();
+        G.k1 = c->pb[PB_KEY1].as<unsigned long long>();
+    }
     const int grid = c->n_lr < c->n_cu * 4 ? c->n_lr : c->n_cu * 4;
     HIPCHK(hipMemsetAsync(c->pb[2].p, 0, (size_t)c->n_lr * 4, c->stream));
     if (o->bin_size > 0 && o->bin_length > 0) {   // bwa-proovread -b/-l (bin/proovread:1302-1313)
@@ -1197,8 +1229,9 @@ extern "C" int pr_iter_launch(pr_ctx *c, const pr_sw_opts *o, const pr_cns_param
         if (e) return set_error(PR_ERR_HIP, "-b/-l filter kernel: %s", hipGetErrorString((hipError_t)e));
     }
     c->cns_gathered = false;   // the hand-off writes offsets into the SW / short-read pools
-    int e = pipe_launch(P, grid, (void *)c->stream, c->pipe_sort_cap * 8);
+    int e = pipe_launch(P, grid, (void *)c->stream, c->pipe_sort_cap * 8, ho.n_big ? &G : nullptr);
     if (e) return set_error(PR_ERR_HIP, "pipe kernels: %s", hipGetErrorString((hipError_t)e));
+    c->ho_done = true;
     return pr_cns_launch(c, p);
 }
 
@@ -1308,6 +1341,42 @@ extern "C" int pr_iter_download_range(pr_ctx *c, int32_t first, int32_t n, pr_cn
     HIPCHK(hipStreamSynchronize(s));
     for (size_t i = 0; i < m; ++i)
         if (err[i]) return set_error(PR_ERR_CAPACITY, "hand-off of long read %d failed (code %d)", first + (int)i, err[i]);
+    return 0;
+}
+
+extern "C" int pr_iter_handoff_stats(pr_ctx *c, int64_t *big_reads, int64_t *big_alns, int32_t *max_alns) {
+    if (!c) return set_error(PR_ERR_ARG, "null ctx");
+    if (!c->pipe || !c->ho_done) return set_error(PR_ERR_ARG, "no hand-off yet (pr_iter_launch first)");
+    if (big_reads) *big_reads = c->ho.n_big;   // the host's plan: no device access
+    if (!big_alns && !max_alns) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<int32_t> cnt((size_t)c->n_lr + 1, 0);
+    if (c->n_lr) HIPCHK(hipMemcpyAsync(cnt.data(), c->pb[PB_CNT].p, (size_t)c->n_lr * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    int64_t ba = 0;
+    int32_t mx = 0;
+    for (int32_t lr : c->ho.big_lr) ba += cnt[(size_t)lr];
+    for (int i = 0; i < c->n_lr; ++i) mx = std::max(mx, cnt[(size_t)i]);
+    if (big_alns) *big_alns = ba;
+    if (max_alns) *max_alns = mx;
+    return 0;
+}
+
+extern "C" int pr_iter_handoff_order(pr_ctx *c, int32_t lr, int32_t *task_idx, int64_t cap, int64_t *n) {
+    if (!c || !n) return set_error(PR_ERR_ARG, "null arg");
+    if (!c->pipe || !c->ho_done) return set_error(PR_ERR_ARG, "no hand-off yet (pr_iter_launch first)");
+    if (lr < 0 || lr >= c->n_lr) return set_error(PR_ERR_ARG, "long read %d outside the batch", lr);
+    HIPCHK(hipSetDevice(c->device));
+    int64_t a[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(a, c->cb[CB_ALN_OFF].as<int64_t>() + lr, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *n = a[1] - a[0];
+    if (!task_idx) return 0;
+    if (*n > cap) return set_error(PR_ERR_CAPACITY, "hand-off order: %lld alignments, room for %lld", (long long)*n, (long long)cap);
+    if (*n) {
+        HIPCHK(hipMemcpyAsync(task_idx, c->pb[PB_ORDER].as<int32_t>() + a[0], (size_t)*n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
     return 0;
 }
 

@@ -1265,7 +1265,8 @@ static int bwa_group(pr_ctx *c, SwResident &r, SwPtrs *p) {
     G.o_strand = strand;
     G.o_pass = pass;
     if ((e = sw_launch_gather(G, (void *)s))) return pr_set_error(PR_ERR_HIP, hipGetErrorString((hipError_t)e));
-    std::vector<int32_t> cnt(l1, 0);
+    std::vector<int32_t> &cnt = r.gcnt_host;
+    cnt.assign(l1, 0);
     HIPCHK(hipMemcpyAsync(cnt.data(), r.buf[SB_GCNT], l1 * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     int mx = 0;
@@ -1282,6 +1283,7 @@ static int bwa_group(pr_ctx *c, SwResident &r, SwPtrs *p) {
     p->n_task = n;
     p->task_off = (const int64_t *)r.buf[SB_GLROFF];
     p->max_per_lr = mx;
+    p->cnt_host = cnt.data();
     return 0;
 }
 
@@ -1310,6 +1312,7 @@ int sw_get_ptrs(pr_ctx *c, SwPtrs *p) {
     if (!r.loaded) return pr_set_error(PR_ERR_ARG, "no resident SW batch");
     p->task_off = nullptr;
     p->max_per_lr = 0;
+    p->cnt_host = nullptr;
     p->sr = (const uint8_t *)r.buf[SB_SR];
     p->lr = lr_pool(r);
     p->strand = (const uint8_t *)r.buf[SB_T_STRAND];

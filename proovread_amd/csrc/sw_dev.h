@@ -3,6 +3,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 #ifdef __HIPCC__
 #define SW_HD __host__ __device__
 #else
@@ -113,6 +115,7 @@ struct SwResident {
     int64_t n_rank0 = 0;        // first seeds of the chains (the first round)
     bool cnext_ready = false;   // cnext written by the device-seed unpack (seed ranks)
     int64_t n_big = 0;          // bwa mode: reads of more than ALN_WAVE_SEEDS seeds (the lane kernels')
+    std::vector<int32_t> gcnt_host;   // bwa mode: reported alignments per long read of the last regrouping
     void *side = nullptr;       // hipStream_t: the early final pass beside the later extension rounds
     void *side_ev[3] = {nullptr, nullptr, nullptr};   // hipEvent_t
     int64_t n_patch = 0;        // mem_patch_reg global scores computed
@@ -141,6 +144,7 @@ struct SwPtrs {
     int n_sr, n_lr;
     const int64_t *task_off;    // bwa mode: [n_lr+1] alignments of long read i; else null
     int max_per_lr;             // bwa mode: most alignments on one long read
+    const int32_t *cnt_host;    // bwa mode: [n_lr] alignments of each long read, on the host
 };
 
 int sw_launch_order(const SwDev &D, const SwOptsDev &O, int phase, int32_t *out, void *stream);

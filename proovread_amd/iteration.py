@@ -37,6 +37,8 @@ def _setup(L):
     L.pr_iter_stats.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     L.pr_ctx_sync.argtypes = [C.c_void_p]
     L.pr_iter_alignment_stats.argtypes = [C.c_void_p, _abi.P64, _abi.P64, _abi.P64]
+    L.pr_iter_handoff_stats.argtypes = [C.c_void_p, _abi.P64, _abi.P64, _abi.P32]
+    L.pr_iter_handoff_order.argtypes = [C.c_void_p, C.c_int32, _abi.P32, C.c_int64, _abi.P64]
     L.pr_sw_upload_gpu_seeds.argtypes = [C.c_void_p, C.POINTER(sw.SwBatch)]
     L.pr_aln_exchange.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, _abi.P64, _abi.P64]
     L.pr_aln_exchange_local.argtypes = [C.c_void_p, C.c_int, _abi.P64, _abi.P64, _abi.P64]
@@ -164,6 +166,25 @@ class Iteration:
         v = [C.c_int64() for _ in range(3)]
         _abi.check(self.L.pr_iter_alignment_stats(self.ctx.h, *[C.byref(x) for x in v]), "alignment_stats")
         return [x.value for x in v]
+
+    def handoff_stats(self, counts: bool = True):
+        """The last launch's hand-off: reads sorted through HBM (more than 16,384 alignments before
+        the filters), their alignments and the most alignments on one read after the filters
+        (counts False: the first only, without a device synchronise; the others None)."""
+        br, ba, mx = C.c_int64(), C.c_int64(), C.c_int32()
+        _abi.check(self.L.pr_iter_handoff_stats(self.ctx.h, C.byref(br), C.byref(ba) if counts else None,
+                                                C.byref(mx) if counts else None), "pr_iter_handoff_stats")
+        return SimpleNamespace(big_reads=br.value, big_alns=ba.value if counts else None,
+                               max_alns=mx.value if counts else None)
+
+    def handoff_order(self, lr: int) -> np.ndarray:
+        """Test hook: long read lr's alignments in hand-off order, as indexes among its tasks."""
+        n = C.c_int64()
+        _abi.check(self.L.pr_iter_handoff_order(self.ctx.h, lr, None, 0, C.byref(n)), "pr_iter_handoff_order")
+        out = np.zeros(max(n.value, 1), np.int32)
+        _abi.check(self.L.pr_iter_handoff_order(self.ctx.h, lr, _abi.ptr(out, C.c_int32), n.value, C.byref(n)),
+                   "pr_iter_handoff_order")
+        return out[:n.value]
 
     def timing(self):
         v = [C.c_double() for _ in range(4)]
