@@ -724,6 +724,29 @@ typedef struct pr_bam_alns {
 } pr_bam_alns;
 int pr_bam_decode_alns(const uint8_t *recs, int64_t len, int n_threads, pr_bam_alns *out);
 void pr_bam_alns_free(pr_bam_alns *a);
+/* The same decoder on the device (bam_kernels.hip: one lane per record for the fields and the aux
+ * walk, scans for the pool offsets, a 16-lane group per record for SEQ / QUAL / CIGAR), its
+ * columns downloaded: the contract of pr_bam_decode_alns, so the two can be compared field by
+ * field.  The host reads only the records' sizes (same three size errors) and numifies AS:Z.  */
+int pr_bam_decode_alns_gpu(pr_ctx *ctx, const uint8_t *recs, int64_t len, pr_bam_alns *out);
+/* proovread's sam / bam modes (read-sam / read-bam, bin/proovread:718-736, 994-1025): the
+ * consensus batch straight from a coordinate-sorted record stream.  reads carries the long-read
+ * fields only (n_lr, lr_off, ref_seq, ref_qual, ign_off, ign; alignment fields NULL); ref_to_lr
+ * [n_ref] maps a BAM reference id to a read of the batch or -1 (no two references to one read).
+ * Records with rid -1 or a reference mapped to -1 are dropped; the others are decoded and grouped
+ * per long read on the device, each read's records in file order (bam2cns's region order), and
+ * stay resident exactly as after pr_cns_upload: pr_cns_launch / pr_cns_download follow.
+ * PR_ERR_ARG "not coordinate-sorted" when the kept records' reference ids decrease somewhere,
+ * PR_ERR_NOSEQ for a kept record without SEQ (bam2cns:347), PR_ERR_SAM for a bad aux field.   */
+int pr_cns_upload_bam(pr_ctx *ctx, const pr_cns_batch *reads, const uint8_t *recs, int64_t len,
+                      const int32_t *ref_to_lr, int32_t n_ref, int64_t *n_kept);
+/* pr_cns_bounds_of for the resident batch (pr_cns_upload or pr_cns_upload_bam); its alignments:
+ * the count and (aln_off [n_lr + 1], may be NULL) the per-read prefix pr_cns_out.kept follows */
+int pr_cns_resident_bounds(pr_ctx *ctx, pr_cns_bounds *out);
+int pr_cns_resident_aln_count(pr_ctx *ctx, int64_t *n_aln, int64_t *aln_off);
+/* milliseconds of the decode kernels (HIP events on the ctx stream) of the last
+ * pr_cns_upload_bam / pr_bam_decode_alns_gpu */
+int pr_bam_decode_last_ms(pr_ctx *ctx, double *ms);
 /* `samtools index` (bin/proovread:1343-1355): the BAI bytes of a coordinate-sorted BAM file
  * (bins + chunks, pseudo-bin 37450, 16 kb linear index, no-coordinate count);
  * PR_ERR_ARG if the file is not coordinate-sorted.                                     */

@@ -88,6 +88,12 @@ def lib():
     L.pr_cns_last_timing.argtypes = [C.c_void_p, PD, PD]
     L.pr_cns_phase_ticks.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
     L.pr_cns_resident_stats.argtypes = [C.c_void_p, P64, P64]
+    # the device BAM decoder (sam / bam modes)
+    L.pr_bam_decode_alns_gpu.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p]
+    L.pr_cns_upload_bam.argtypes = [C.c_void_p, C.POINTER(CnsBatch), C.c_char_p, C.c_int64, P32, C.c_int32, P64]
+    L.pr_cns_resident_bounds.argtypes = [C.c_void_p, C.POINTER(CnsBounds)]
+    L.pr_cns_resident_aln_count.argtypes = [C.c_void_p, P64, P64]
+    L.pr_bam_decode_last_ms.argtypes = [C.c_void_p, PD]
     _lib = L
     return L
 

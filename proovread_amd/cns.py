@@ -284,10 +284,13 @@ def make_c_batch(d: Dict[str, np.ndarray]) -> _abi.CnsBatch:
 class OutBuffers:
     """Host output buffers sized by pr_cns_bounds_of."""
 
-    def __init__(self, d: Dict[str, np.ndarray], cb: _abi.CnsBatch, bin_size: float = 20.0):
+    def __init__(self, d: Dict[str, np.ndarray], cb: _abi.CnsBatch, bin_size: float = 20.0,
+                 bounds: Optional[_abi.CnsBounds] = None):
         L = _abi.lib()
-        bd = _abi.CnsBounds()
-        _abi.check(L.pr_cns_bounds_of(C.byref(cb), C.byref(bd)), "pr_cns_bounds_of")
+        bd = bounds   # given: those of a resident batch (pr_cns_resident_bounds)
+        if bd is None:
+            bd = _abi.CnsBounds()
+            _abi.check(L.pr_cns_bounds_of(C.byref(cb), C.byref(bd)), "pr_cns_bounds_of")
         n = cb.n_lr
         na = int(d["aln_off"][-1])
         lens = np.diff(d["lr_off"])
@@ -366,6 +369,94 @@ def run_packed(reads: Sequence[LongRead], d: Dict[str, np.ndarray], params: CnsP
             if r.status != 0:
                 raise RuntimeError(f"{r.id}: {_abi.ERRORS.get(r.status, r.status)}")
     return res
+
+
+def run_bam(reads: Sequence[LongRead], bam_path: str, params: CnsParams, ctx: Optional[_abi.Context] = None,
+            raise_on_error: bool = False, split: int = 1, threads: int = 0) -> List[ReadResult]:
+    """The consensus of every read over a coordinate-sorted BAM file (proovread's read-bam task,
+    bin/proovread:994-1025 + correct_sr_mt, without the chunk fan-out): the file is inflated on
+    host threads, its records are decoded and grouped per read on the device
+    (pr_cns_upload_bam), then one consensus launch.  Results as run_packed's."""
+    from . import bamio
+    with open(bam_path, "rb") as fh:
+        stream = bamio._native_inflate(fh.read(), threads)
+    h, o = bamio._parse_header(stream)
+    return run_bam_records(reads, [nm for nm, _ in h.refs], stream[o:], params, ctx, raise_on_error, split)
+
+
+def run_bam_records(reads: Sequence[LongRead], names: Sequence[str], body: bytes, params: CnsParams,
+                    ctx: Optional[_abi.Context] = None, raise_on_error: bool = False, split: int = 1) -> List[ReadResult]:
+    """run_bam on the reference names of a BAM header and its record stream (block_size-prefixed
+    records in coordinate order).  A read takes the records whose reference is named as its id;
+    of reads that share an id the first takes them in this pass and the others in a pass of their
+    own (pack_bam_chunk gives a repeated id the same records).  split: the reads go in that many
+    contiguous ranges, the stream being decoded once per range; a range that does not fit in the
+    device memory (hipMalloc fails) is halved until it does."""
+    ctx = ctx or _abi.default_context()
+    reads = list(reads)
+    first: Dict[str, int] = {}
+    rest = []
+    for i, r in enumerate(reads):
+        if r.id in first:
+            rest.append(i)
+        else:
+            first[r.id] = i
+    main = sorted(first.values())
+    out: List[Optional[ReadResult]] = [None] * len(reads)
+    n = len(main)
+    bounds = [n * k // max(1, split) for k in range(max(1, split) + 1)] if n else [0, 0]
+    todo = [(bounds[k], bounds[k + 1]) for k in range(len(bounds) - 1) if bounds[k + 1] > bounds[k]]
+    while todo:
+        lo, hi = todo.pop(0)
+        sub = [reads[main[k]] for k in range(lo, hi)]
+        try:
+            res = _run_bam_range(sub, names, body, params, ctx)
+        except RuntimeError as e:
+            if "hipMalloc" not in str(e) or hi - lo < 2:
+                raise
+            mid = (lo + hi) // 2
+            todo[:0] = [(lo, mid), (mid, hi)]
+            continue
+        for k, r in zip(range(lo, hi), res):
+            out[main[k]] = r
+    if rest:
+        for i, r in zip(rest, run_bam_records([reads[i] for i in rest], names, body, params, ctx, False, split)):
+            out[i] = r
+    if raise_on_error:
+        for r in out:
+            if r.status != 0:
+                raise RuntimeError(f"{r.id}: {_abi.ERRORS.get(r.status, r.status)}")
+    return out
+
+
+def _run_bam_range(reads: Sequence[LongRead], names: Sequence[str], body: bytes, params: CnsParams,
+                   ctx: _abi.Context) -> List[ReadResult]:
+    """One resident batch: reads with distinct ids, their records from the stream."""
+    L = _abi.lib()
+    n = len(reads)
+    d = pack_reads(reads)
+    d["aln_off"] = np.zeros(n + 1, np.int64)
+    idx = {r.id: i for i, r in enumerate(reads)}
+    r2l = np.array([idx.get(nm, -1) for nm in names], np.int32)
+    cb = _abi.CnsBatch()
+    P = _abi.ptr
+    cb.n_lr = n
+    cb.lr_off = P(d["lr_off"], C.c_int64)
+    cb.ref_seq = P(d.get("ref_seq"), C.c_uint8)
+    cb.ref_qual = P(d.get("ref_qual"), C.c_uint8)
+    cb.ign_off = P(d.get("ign_off"), C.c_int64)
+    cb.ign = P(d.get("ign"), C.c_int32)
+    nk = C.c_int64()
+    _abi.check(L.pr_cns_upload_bam(ctx.h, C.byref(cb), body, len(body), P(r2l, C.c_int32) if len(r2l) else None,
+                                   len(r2l), C.byref(nk)), "pr_cns_upload_bam")
+    _abi.check(L.pr_cns_resident_aln_count(ctx.h, None, P(d["aln_off"], C.c_int64)), "pr_cns_resident_aln_count")
+    bd = _abi.CnsBounds()
+    _abi.check(L.pr_cns_resident_bounds(ctx.h, C.byref(bd)), "pr_cns_resident_bounds")
+    ob = OutBuffers(d, cb, params.bin_size, bounds=bd)
+    pc = params.to_c()
+    _abi.check(L.pr_cns_launch(ctx.h, C.byref(pc)), "pr_cns_launch")
+    _abi.check(L.pr_cns_download(ctx.h, C.byref(ob.c)), "pr_cns_download")
+    return ob.results([r.id for r in reads], d)
 
 
 class SamSeq:

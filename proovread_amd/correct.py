@@ -20,6 +20,9 @@ hot stages on the device:
   bwa-sr-finish    (proovread:838-850, 1572-1577) 30x sampling, finish scoring,
                    unmasked reference, --no-use-ref-qual, --max-ins-length 0,
                    --detect-chimera
+  read-sam / read-bam  (proovread:718-736; modes sam / bam, --sam / --bam) alignments made
+                   elsewhere: one consensus of every long read over the file, its BAM
+                   records decoded and grouped per read on the device (cns.run_bam)
 
 The device stages are behind `GpuStages` (the product; it fails loudly without
 libprgpu.so and a gfx950 device).  Tests drive the same loop with the CPU oracle
@@ -76,6 +79,8 @@ class LoopConfig:
     bin_filter: bool = True                # bwa-proovread -b/-l in every iteration (proovread:1302-1313)
     exact_layout: bool = False             # world 1: run the multi-GPU exact-parity layout anyway (tests)
     keep_masked: bool = False              # LoopResult.masked: the last regular task's masked reads
+    sam: Optional[str] = None              # --sam: alignments made elsewhere (mode sam, task read-sam)
+    bam: Optional[str] = None              # --bam: the same as a coordinate-sorted BAM (mode bam, task read-bam)
 
 
 class LongReads:
@@ -427,6 +432,39 @@ class GpuStages:
         self.last_iteration = it   # the task's consensus outputs stay readable (tests, drivers)
         return out
 
+    def external_alignments(self, task: str, path: str, params) -> TaskOut:
+        """read-sam / read-bam (bin/proovread:718-736): the consensus of every long read over
+        alignments made elsewhere, in place of correct_sr_mt's bam2cns chunk fan-out.  read-bam
+        takes a coordinate-sorted BAM as it is (the reference runs `samtools index` on it);
+        read-sam is `samtools view -bS` + `samtools sort` on the host (pr_sam_encode,
+        pr_bam_sort_records, bin/proovread:994-1025 + create_sorted_bam), then the same path.
+        The records are decoded and grouped per read on the device (cns.run_bam_records); the
+        consensus replaces the resident reads."""
+        from . import _abi, bamio, cns
+        cur = self.reads()
+        lrs = [cns.LongRead(i, s.decode("latin-1"), q.decode("latin-1")) for i, s, q in zip(cur.ids, cur.seqs, cur.quals)]
+        if task == "read-sam":
+            with open(path, encoding="latin-1") as fh:
+                text = fh.read()
+            head = "".join(ln + "\n" for ln in text.split("\n") if ln.startswith("@"))
+            names = [nm for nm, _ in bamio.Header.from_sam_text(head).refs]
+            body = bamio._native_sort(bamio._native_encode(text, names))
+        else:
+            with open(path, "rb") as fh:
+                stream = bamio._native_inflate(fh.read())
+            h, o = bamio._parse_header(stream)
+            names, body = [nm for nm, _ in h.refs], stream[o:]
+        res = cns.run_bam_records(lrs, names, body, params, ctx=self.ctx)
+        for r in res:
+            if r.status != 0:   # bam2cns exits (Verbose->exit) and proovread stops
+                raise RuntimeError(f"{task}: {r.id}: consensus failed ({_abi.ERRORS.get(r.status, r.status)})")
+        ms = C.c_double()
+        _abi.check(_abi.lib().pr_bam_decode_last_ms(self.ctx.h, C.byref(ms)), "pr_bam_decode_last_ms")
+        self.device_ms += ms.value
+        self.last_stage_ms = {"bam_decode": round(ms.value, 2)}
+        self.load(LongReads(cur.ids, [r.seq.encode("latin-1") for r in res], [r.qual.encode("latin-1") for r in res]))
+        return TaskOut(int(sum(len(r.kept) for r in res)), [ln for r in res for ln in r.chim_lines()])
+
     def reads(self) -> LongReads:
         off, seq, qual, _ = self.lrs.download(seq=True, qual=True)
         return LongReads(self.ids, pools=(seq, off, qual))
@@ -496,6 +534,16 @@ Comm = TorchComm
 
 
 # ---------------------------------------------------------------------------- the loop
+def mode_of(cfg: LoopConfig) -> Optional[str]:
+    """bin/proovread:628-632: --bam selects mode bam, --sam mode sam, whatever --mode says;
+    otherwise --mode, or None (by short-read length, proovread:636-642)."""
+    if cfg.bam:
+        return "bam"
+    if cfg.sam:
+        return "sam"
+    return cfg.mode
+
+
 def run(lr_records: Sequence[Tuple[str, bytes, Optional[bytes]]], sr_data: bytes, cfg: Optional[LoopConfig] = None,
         stages=None, comm=None) -> LoopResult:
     """The sr-noccs loop (bin/proovread:705-905) from long-read records and the short-read
@@ -507,7 +555,7 @@ def run(lr_records: Sequence[Tuple[str, bytes, Optional[bytes]]], sr_data: bytes
     srs = ShortReads(sr_data)
     min_sr = cfg.min_sr_length or (int(srs.lengths.min()) if len(srs.lengths) else 200)
     stubby = cfg.lr_min_length if cfg.lr_min_length is not None else 2 * min_sr
-    mode = cfg.mode or T.mode_for(min_sr)
+    mode = mode_of(cfg) or T.mode_for(min_sr)
     tasks = list(cfg.tasks or T.MODE_TASKS[mode])
     ids: List[str] = []
     ignored: List[str] = []
@@ -516,7 +564,7 @@ def run(lr_records: Sequence[Tuple[str, bytes, Optional[bytes]]], sr_data: bytes
         reads, ignored = read_long(lr_records, stubby)
         ids = reads.ids
         stages.load(reads)    # the mapping reference starts as the reads (.masked.fa)
-        if hasattr(stages, "load_short_reads"):
+        if hasattr(stages, "load_short_reads") and len(srs.lengths):
             stages.load_short_reads(srs)
         log.append(TaskLog("read-long"))
         tasks = tasks[1:]
@@ -548,6 +596,29 @@ def run_tasks(stages, srs: ShortReads, tasks: List[str], cfg: LoopConfig, mode: 
     tc = 0
     while tc < len(tasks):   # proovread:705 (tasks may shrink: mask_shortcut_frac splices)
         task = tasks[tc]
+        if task in ("read-sam", "read-bam"):   # proovread:718-736: external alignments, one consensus pass
+            if comm is not None and comm.world > 1:
+                raise ValueError(f"task {task} runs on one GPU")
+            path = cfg.sam if task == "read-sam" else cfg.bam
+            if not path:
+                raise ValueError(f"task {task} needs --{task[5:]}")
+            ent = TaskLog(task)
+            t_task = time.perf_counter()
+            dev0 = getattr(stages, "device_ms", None)
+            # correct_sr_mt's bam2cns options for the task (proovread:1534-1591)
+            max_cov = min(cfg.coverage, sr_coverage_for(task)) * cfg.coverage_scale_factor
+            params = cns.CnsParams(coverage=max_cov, bin_size=float(T.bin_size(mode)), use_ref_qual=True,
+                                   detect_chimera=T.detect_chimera(task), max_ins_length=0)
+            r = stages.external_alignments(task, path, params) if have_reads else TaskOut(0, [])
+            ent.n_tasks = r.n_tasks
+            chim += r.chim
+            ent.wall_ms = round((time.perf_counter() - t_task) * 1e3, 1)
+            if dev0 is not None:
+                ent.device_ms = round(stages.device_ms - dev0, 1)
+                ent.stage_ms = getattr(stages, "last_stage_ms", None)
+            log.append(ent)
+            tc += 1
+            continue
         if not (task.startswith("bwa-sr") or task.startswith("bwa-mr")):
             raise ValueError(f"task {task} is outside the sr / mr loops")
         finish = task.endswith("-finish")
@@ -638,20 +709,18 @@ def write_outputs(res: LoopResult, pre: str, min_length: int = 500, trim_win: st
 
 
 # ---------------------------------------------------------------------------- command line
-def main(argv: Optional[Sequence[str]] = None) -> int:
-    """python -m proovread_amd.correct -l LR.fq -s SR.fq [-s ...] --pre OUT [--coverage C]
-
-    Writes write_outputs' files (OUT.untrimmed.fq, OUT.trimmed.fq/.fa, OUT.chim.tsv,
-    OUT.ignored.tsv).
-    Launched with torch.distributed.run (one rank per GPU), the ranks split the work as
-    Comm describes and rank 0 writes the files."""
+def parse_args(argv: Optional[Sequence[str]] = None):
+    """The command line of main().  -l is always required (bin/proovread:346); -s unless
+    --sam / --bam hand in alignments made elsewhere (proovread:347-350); the mode follows
+    --bam, then --sam, then -m (proovread:628-632)."""
     import argparse
     import os
-    import sys
-    from .bwa_proovread import read_fastx
     ap = argparse.ArgumentParser(prog="proovread_amd.correct")
     ap.add_argument("-l", "--long-reads", action="append", required=True)
-    ap.add_argument("-s", "--short-reads", action="append", required=True)
+    ap.add_argument("-s", "--short-reads", action="append", default=[])
+    ap.add_argument("--sam", metavar="FILE", help="correct from the alignments of a SAM file (mode sam)")
+    ap.add_argument("--bam", metavar="FILE", help="correct from a coordinate-sorted BAM file (mode bam)")
+    ap.add_argument("-m", "--mode", choices=sorted(T.MODE_TASKS), help="the task list (default: by short-read length)")
     ap.add_argument("-p", "--pre", required=True)
     ap.add_argument("--coverage", type=float, default=50.0)
     ap.add_argument("--no-sampling", action="store_true")
@@ -659,12 +728,36 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--siamaera", action="store_true",
                     help="pass the trimmed reads through the siamaera stage (the reference's default)")
     a = ap.parse_args(argv)
+    if not (a.short_reads or a.sam or a.bam):
+        ap.error("either -s/--short-reads or --sam / --bam is required")
+    for opt, f in (("--sam", a.sam), ("--bam", a.bam)):
+        if f and not os.path.isfile(f):
+            ap.error(f"cannot find {opt[2:].upper()} file `{f}`")
+    a.mode = mode_of(LoopConfig(mode=a.mode, sam=a.sam, bam=a.bam))
+    if a.mode in ("sam", "bam") and not (a.sam or a.bam):
+        ap.error(f"mode {a.mode} needs --{a.mode}")
+    return a
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    """python -m proovread_amd.correct -l LR.fq (-s SR.fq [-s ...] | --sam X.sam | --bam X.bam)
+    --pre OUT [--coverage C] [-m MODE]
+
+    Writes write_outputs' files (OUT.untrimmed.fq, OUT.trimmed.fq/.fa, OUT.chim.tsv,
+    OUT.ignored.tsv).
+    Launched with torch.distributed.run (one rank per GPU), the ranks split the work as
+    Comm describes and rank 0 writes the files (the sam / bam modes run on one GPU)."""
+    import os
+    import sys
+    from .bwa_proovread import read_fastx
+    a = parse_args(argv)
     lrs = []
     for f in a.long_reads:
         names, seqs, quals = read_fastx(f)
         lrs += list(zip(names, seqs, quals))
     sr_data = b"".join(open(f, "rb").read() for f in a.short_reads)
-    cfg = LoopConfig(coverage=a.coverage, sampling=not a.no_sampling, seed_threads=a.threads)
+    cfg = LoopConfig(coverage=a.coverage, sampling=not a.no_sampling, seed_threads=a.threads, mode=a.mode,
+                     sam=a.sam, bam=a.bam)
     comm, rank = None, 0
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         from . import _abi

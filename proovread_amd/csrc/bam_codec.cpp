@@ -478,6 +478,9 @@ static double perl_number(const char *s, const char *e) {
     return std::strtod(std::string(b, p).c_str(), nullptr);
 }
 
+// perl_number for the device decoder's host part (bam_api.cpp: AS:Z scores)
+double bam_perl_number(const char *s, const char *e) { return perl_number(s, e); }
+
 // BAM record stream -> the per-alignment arrays of the consensus stage (bam2cns's BAM
 // reader, proovread_amd/bam2cns.py:bam_records + cns.py:pack_chunk): POS, AS, flags, SEQ as
 // printed ("=ACMGRSVTWYHKDBN"), QUAL as phred+33 ('!' for a missing one), CIGAR ops.

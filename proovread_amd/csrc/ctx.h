@@ -133,6 +133,8 @@ struct pr_ctx {
     bool has_ref = false, has_qual = false, has_ign = false;
     std::vector<int64_t> out_off, chim_off, bin_off, lr_off_host;
     float last_ms = 0.f;
+    std::vector<int64_t> aln_off_host;   // the resident batch's alignment offsets (pr_cns_upload / pr_cns_upload_bam)
+    float ms_bam = 0.f;                  // decode kernels of the last pr_cns_upload_bam / pr_bam_decode_alns_gpu
     // SW -> consensus pipeline (pr_iter_*)
     bool pipe = false;
     bool pipe_ref_ascii = false;   // pr_iter_batch.ref_seq given: consensus reference in CB_REF_SEQ
@@ -193,6 +195,11 @@ static int download(T *h, const DevBuf &d, size_t n, hipStream_t s, size_t first
     if (h && n) HIPCHK(hipMemcpyAsync(h, d.as<T>() + first, n * sizeof(T), hipMemcpyDeviceToHost, s));
     return 0;
 }
+
+// the two halves of pr_cns_upload that pr_cns_upload_bam shares (prgpu_api.cpp): the long-read part
+// of a batch, and the scratch / output buffers once the alignment columns and bounds are set
+int cns_upload_long_reads(pr_ctx *c, const pr_cns_batch *b);
+int cns_alloc_resident(pr_ctx *c);
 
 // the seed index built in HBM (seed_api.cpp); lr_dev: lr_seq is a device pointer (pr_lrset_index)
 int index_build(pr_ctx *c, const uint8_t *lr_seq, const int64_t *lr_off, int n_lr, bool lr_dev);

@@ -250,26 +250,45 @@ extern "C" int pr_cns_bounds_of(const pr_cns_batch *b, pr_cns_bounds *out) {
     return 0;
 }
 
-extern "C" int pr_cns_upload(pr_ctx *c, const pr_cns_batch *b) {
-    if (!c) return set_error(PR_ERR_ARG, "null ctx");
-    int rc = validate_batch(b);
-    if (rc) return rc;
+// the long-read part of a resident consensus batch: lengths, reference, qualities, MCR ranges
+int cns_upload_long_reads(pr_ctx *c, const pr_cns_batch *b) {
     c->cns_launched = false;
     c->iter_masked = false;
     c->own = false;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const int n = b->n_lr;
-    const int64_t na = n ? b->aln_off[n] : 0;
     const int64_t tl = n ? b->lr_off[n] : 0;
     c->n_lr = n;
-    c->n_aln = na;
     c->total_cols = tl;
     c->pipe = false;
-    c->lr_off_host.assign(b->lr_off, b->lr_off + n + 1);
+    if (n) c->lr_off_host.assign(b->lr_off, b->lr_off + n + 1);
+    else c->lr_off_host.assign(1, 0);
     c->has_ref = b->ref_seq != nullptr;
     c->has_qual = b->ref_qual != nullptr;
     c->has_ign = b->ign_off != nullptr;
+    int rc;
+    DevBuf *B = c->cb;
+    if ((rc = upload(B[CB_LR_OFF], c->lr_off_host.data(), n + 1, s))) return rc;
+    if ((rc = upload(B[CB_REF_SEQ], b->ref_seq, b->ref_seq ? tl : 0, s))) return rc;
+    if ((rc = upload(B[CB_REF_QUAL], b->ref_qual, b->ref_qual ? tl : 0, s))) return rc;
+    if (b->ign_off) {
+        if ((rc = upload(B[CB_IGN_OFF], b->ign_off, n + 1, s))) return rc;
+        if ((rc = upload(B[CB_IGN], b->ign, 2 * b->ign_off[n], s))) return rc;
+    }
+    return 0;
+}
+
+extern "C" int pr_cns_upload(pr_ctx *c, const pr_cns_batch *b) {
+    if (!c) return set_error(PR_ERR_ARG, "null ctx");
+    int rc = validate_batch(b);
+    if (rc) return rc;
+    if ((rc = cns_upload_long_reads(c, b))) return rc;
+    hipStream_t s = c->stream;
+    const int n = b->n_lr;
+    const int64_t na = n ? b->aln_off[n] : 0;
+    const int64_t tl = c->total_cols;
+    c->n_aln = na;
     int64_t in_bytes = 0;
     cns_caps(b, c->out_off, c->chim_off, &in_bytes, &c->k_need);
     c->seq_cap = c->out_off[n];
@@ -278,13 +297,7 @@ extern "C" int pr_cns_upload(pr_ctx *c, const pr_cns_batch *b) {
     c->alg_bytes = in_bytes + tl * 2 + tl * 2 + tl * 6 * 4 * 2;
 
     DevBuf *B = c->cb;
-    if ((rc = upload(B[CB_LR_OFF], b->lr_off, n + 1, s))) return rc;
-    if ((rc = upload(B[CB_REF_SEQ], b->ref_seq, b->ref_seq ? tl : 0, s))) return rc;
-    if ((rc = upload(B[CB_REF_QUAL], b->ref_qual, b->ref_qual ? tl : 0, s))) return rc;
-    if (b->ign_off) {
-        if ((rc = upload(B[CB_IGN_OFF], b->ign_off, n + 1, s))) return rc;
-        if ((rc = upload(B[CB_IGN], b->ign, 2 * b->ign_off[n], s))) return rc;
-    }
+    c->aln_off_host.assign(b->aln_off, b->aln_off + (n ? n + 1 : 0));
     if ((rc = upload(B[CB_ALN_OFF], b->aln_off, n + 1, s))) return rc;
     if ((rc = upload(B[CB_POS], b->aln_pos, na, s))) return rc;
     if ((rc = upload(B[CB_SCORE], b->aln_score, na, s))) return rc;
@@ -295,8 +308,18 @@ extern "C" int pr_cns_upload(pr_ctx *c, const pr_cns_batch *b) {
     if ((rc = upload(B[CB_NCIG], b->aln_ncig, na, s))) return rc;
     if ((rc = upload(B[CB_SEQ], b->seq_pool, b->seq_pool_len, s))) return rc;
     if ((rc = upload(B[CB_CIG], b->cig_pool, b->cig_pool_len, s))) return rc;
+    return cns_alloc_resident(c);
+}
+
+// scratch and output buffers of the resident batch (c->n_lr, n_aln, out_off, chim_off, seq_cap, chim_cap
+// set), then the batch counts as loaded
+int cns_alloc_resident(pr_ctx *c) {
+    hipStream_t s = c->stream;
+    DevBuf *B = c->cb;
+    const int n = c->n_lr;
+    int rc;
     // per-alignment scratch
-    const size_t na1 = (size_t)na + 1;
+    const size_t na1 = (size_t)c->n_aln + 1;
     if ((rc = B[CB_A_ST].ensure(na1 * 4)) || (rc = B[CB_A_LEN].ensure(na1 * 4)) ||
         (rc = B[CB_A_NC].ensure(na1 * 8)) || (rc = B[CB_A_BIN].ensure(na1 * 4)) ||
         (rc = B[CB_A_CB].ensure(na1 * 4)) || (rc = B[CB_A_CE].ensure(na1 * 4)) ||

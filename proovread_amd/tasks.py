@@ -6,7 +6,8 @@ proovread.cfg is a Perl hash; bin/proovread looks values up with `cfg(KEY, TASK)
 counter, else DEF wins.  This module restates the entries the sr / mr correction loop
 reads, with their cfg lines:
 
-  mode-tasks      proovread.cfg:105-127 (sr-noccs, mr-noccs)
+  mode-tasks      proovread.cfg:105-132 (sr-noccs, mr-noccs; sam, bam: alignments made elsewhere)
+  detect-chimera  proovread.cfg:205-211
   bwa-*           proovread.cfg:318-365 (bwa mem options per task)
   sr-coverage     proovread.cfg:188-192
   hcr-mask        proovread.cfg:234-242
@@ -26,6 +27,9 @@ from typing import Dict, List, Tuple
 MODE_TASKS: Dict[str, Tuple[str, ...]] = {
     "sr-noccs": ("read-long", "bwa-sr-1", "bwa-sr-2", "bwa-sr-3", "bwa-sr-4", "bwa-sr-5", "bwa-sr-6", "bwa-sr-finish"),
     "mr-noccs": ("read-long", "bwa-mr-1", "bwa-mr-2", "bwa-mr-3", "bwa-mr-4", "bwa-mr-5", "bwa-mr-6", "bwa-mr-finish"),
+    # external alignments (--sam / --bam, proovread.cfg:130-132; bin/proovread:170, 718-736)
+    "sam": ("read-long", "read-sam"),
+    "bam": ("read-long", "read-bam"),
 }
 
 # bwa mem option sets (proovread.cfg:318-365); '' = a bare flag
@@ -46,7 +50,10 @@ SR_COVERAGE = {"DEF": 15.0, "bwa-sr-finish": 30.0, "bwa-mr-finish": 30.0}
 HCR_MASK = {"DEF": "20,41,80,130,60,0.7", "bwa-mr-4": "20,41,80,130,60,0.3", "bwa-mr-5": "20,41,80,130,60,0.3",
             "bwa-mr-6": "20,41,80,130,60,0.3", "bwa-sr-4": "20,41,80,130,60,0.3", "bwa-sr-5": "20,41,80,130,60,0.3",
             "bwa-sr-6": "20,41,80,130,60,0.3"}
-BIN_SIZE = {"DEF": 20, "sr": 20, "sr-noccs": 20, "mr": 50, "mr-noccs": 50}
+BIN_SIZE = {"DEF": 20, "sr": 20, "sr-noccs": 20, "mr": 50, "mr-noccs": 50, "sam": 20, "bam": 20}
+# detect-chimera (proovread.cfg:205-211).  The reference lists read-sam but not read-bam, so a BAM
+# run finds no chimeras where the same alignments as SAM do: its quirk, kept.
+DETECT_CHIMERA = {"DEF": 0, "bwa-sr-finish": 1, "bwa-mr-finish": 1, "read-sam": 1}
 
 
 def _strip(task: str) -> str:
@@ -98,6 +105,10 @@ def sr_coverage(task: str) -> float:
 
 def hcr_mask(task: str) -> str:
     return cfg_task(HCR_MASK, task)
+
+
+def detect_chimera(task: str) -> bool:
+    return bool(cfg_task(DETECT_CHIMERA, task))
 
 
 def bin_size(mode: str) -> int:
