@@ -762,6 +762,11 @@ extern "C" int pr_seed_map_device_caps(const pr_seed_index *h, const pr_seed_opt
     auto work = [&]() {
         std::vector<uint64_t> slab((size_t)(bytes / 8 + 1), fill);
         seedc::Scratch S = seedc::carve(reinterpret_cast<uint8_t *>(slab.data()), caps);
+        // the lazy kernel's range-table reuse, here for either table so that the host suite covers
+        // it: cleared once per slab (the kernel: once per launch), every read of the thread then
+        // frees the slots it claimed (seed_core.h chain_seq, Scratch::htab_clean)
+        for (int k = 0; k < S.hsize; ++k) S.htab[k].key = -1;
+        S.htab_clean = true;
         std::vector<pr_seed_task> buf((size_t)caps.out);
         std::vector<uint64_t> big;
         for (;;) {
@@ -776,6 +781,8 @@ extern "C" int pr_seed_map_device_caps(const pr_seed_index *h, const pr_seed_opt
                 cg = seedc::grow_caps(cg, err, 4);
                 big.assign((size_t)(seedc::scratch_bytes(cg) / 8 + 1), fill);
                 seedc::Scratch G = seedc::carve(reinterpret_cast<uint8_t *>(big.data()), cg);
+                for (int k = 0; k < G.hsize; ++k) G.htab[k].key = -1;
+                G.htab_clean = true;
                 err = seedc::map_read(V, *o, G, sr_seq + sr_off[i], len, i, buf.data(), caps.out, &n);
             }
             status[i] = err;

@@ -163,6 +163,9 @@ struct Scratch {
     uint8_t *ready;                            // [lmax + 1] start materialized
     uint64_t *q4w;                             // [lmax / 16 + 4] the read 16 bases per word (4 bits each), or null
     int32_t *lz;                               // [4] pool fill, SC_OVER_* flags, hits the read would need
+    // set by the owner of the scratch: every key of htab is free between reads (the owner cleared
+    // it once; chain_seq then frees the slots a read claimed instead of clearing the table)
+    bool htab_clean;
 };
 
 SC_HD uint64_t pack_ext(const uint8_t *s, int n) {
@@ -872,10 +875,11 @@ SC_HD int collect_intv(const OccT &occ, Scratch &S, const pr_seed_opts &O, const
             }
         }
     }
-    // stable sort by (start, end).  The three rounds each come out sorted by start, so a
-    // counting sort by start (into the seed pool, free until mem_chain; the counts in `codes`,
-    // which nothing reads after the occurrence lookups) and an insertion sort by end inside each
-    // start's run (a few intervals) replace one insertion sort over all ~150 (quadratic moves)
+    // stable sort by (start, end): a counting sort by start (into the seed pool, free until
+    // mem_chain; the counts in `codes`, which nothing reads after the occurrence lookups; any
+    // input order -- the SMEM pass and the -y round come out sorted by start, the re-seeding round
+    // often does not) and an insertion sort by end inside each start's run (a few intervals)
+    // replace one insertion sort over all ~150 (quadratic moves)
     if (nm > 1 && S.cap_seeds >= nm && !err && !S.hend) {   // (the lazy table still needs `codes`)
         static_assert(sizeof(Seed) == sizeof(Iv), "the seed pool holds the sorted intervals");
         int32_t *cnt = S.codes;
@@ -982,24 +986,20 @@ SC_HD void flush_tail(Scratch &S, const RangeRec &R) {
 }
 
 SC_HD int chain_weight(const Scratch &S, const Chain &c) {
-    int64_t end = 0;
-    int w = 0;
-    for (int32_t k = c.head; k >= 0; k = S.seeds[k].nx) {
-        const Seed &s = S.seeds[k];
-        if (s.qbeg >= end) w += s.len;
-        else if (s.qbeg + s.len > end) w += (int)(s.qbeg + s.len - end);
-        end = end > s.qbeg + s.len ? end : s.qbeg + s.len;
+    // the query cover and the reference cover in one walk over the seeds
+    int64_t qe = 0, re = 0;
+    int wq = 0, wr = 0;
+    for (int32_t k = c.head; k >= 0;) {
+        const Seed s = S.seeds[k];
+        if (s.qbeg >= qe) wq += s.len;
+        else if (s.qbeg + s.len > qe) wq += (int)(s.qbeg + s.len - qe);
+        qe = qe > s.qbeg + s.len ? qe : s.qbeg + s.len;
+        if (s.rbeg >= re) wr += s.len;
+        else if (s.rbeg + s.len > re) wr += (int)(s.rbeg + s.len - re);
+        re = re > s.rbeg + s.len ? re : s.rbeg + s.len;
+        k = s.nx;
     }
-    const int tmp = w;
-    w = 0;
-    end = 0;
-    for (int32_t k = c.head; k >= 0; k = S.seeds[k].nx) {
-        const Seed &s = S.seeds[k];
-        if (s.rbeg >= end) w += s.len;
-        else if (s.rbeg + s.len > end) w += (int)(s.rbeg + s.len - end);
-        end = end > s.rbeg + s.len ? end : s.rbeg + s.len;
-    }
-    w = w < tmp ? w : tmp;
+    const int w = wr < wq ? wr : wq;
     return w < (1 << 30) ? w : (1 << 30) - 1;
 }
 
@@ -1123,16 +1123,30 @@ SC_HD int map_chains(const IndexView &I, const pr_seed_opts &O, Scratch &S, cons
 }
 
 // mem_chain over the SMEMs S.mems[0, nm) -> the chains S.cv[0, *n_cv) in creation order
-// (one thread); 0 or SC_OVER_SEEDS / SC_OVER_CHAINS
+// (one thread); 0 or SC_OVER_SEEDS / SC_OVER_CHAINS.
+// S.htab_clean: every key of the range table is free already (the owner of the scratch cleared
+// it once and every read so far left it so): no clear; each range records the slot it claims
+// (RangeRec::pad[0]) and every return frees exactly those -- a finish-task read's ~35 ranges
+// instead of the table's 1,024 or more entries.  The lazy kernel's lanes and the host run of the
+// device path take it; the eager kernel keeps the clear (its ~110 probes per read then hit the
+// lines the clear just wrote: measured 6 ms slower per bwa-sr-1 launch without).
 template <bool LZ>
 SC_HD int chain_seq(const IndexView &I, const pr_seed_opts &O, Scratch &S, int nm, int *n_cv) {
+    const bool clean_on_entry = S.htab_clean;
     int32_t ns = 0, ncv = 0, nrg = 0;
-    for (int k = 0; k < S.hsize; ++k) S.htab[k].key = -1;
+    if (!clean_on_entry)
+        for (int k = 0; k < S.hsize; ++k) S.htab[k].key = -1;
+    // every way out: the table left as it was found
+    auto leave = [&](int rc) {
+        if (clean_on_entry)
+            for (int r = 0; r < nrg; ++r) S.htab[S.rg[r].pad[0]].key = -1;
+        return rc;
+    };
     for (int mi = 0; mi < nm; ++mi) {
         const Iv p = S.mems[mi];
         const int slen = p.end - p.start;
         // (lazy table: every SMEM's start was counted by the SMEM search, so it is materialized)
-        if (LZ && !S.ready[p.start]) return SC_OVER_HITS;
+        if (LZ && !S.ready[p.start]) return leave(SC_OVER_HITS);
         const int32_t h0 = S.hoff[p.start], h1 = LZ ? S.hend[p.start] : S.hoff[p.start + 1];
         // the SMEM's occurrence count is the number of the start's hits with ml >= slen
         // (every interval's occ comes from the same per-start table, slen >= 12)
@@ -1207,13 +1221,13 @@ SC_HD int chain_seq(const IndexView &I, const pr_seed_opts &O, Scratch &S, int n
                     if (at >= 0) {
                         const int r = at_tail ? merge_tail(O, I.l_pac, S, ns, R, s)
                                               : test_and_merge(O, I.l_pac, S, ns, S.cv[at], s, rid);
-                        if (r < 0) return SC_OVER_SEEDS;
+                        if (r < 0) return leave(SC_OVER_SEEDS);
                         if (r) { SC_STAT(5, 1); continue; }
                     }
                 }
                 SC_STAT(6, 1);
-                if (ncv >= S.cap_chains) return SC_OVER_CHAINS;
-                if (ns >= S.cap_seeds) return SC_OVER_SEEDS;
+                if (ncv >= S.cap_chains) return leave(SC_OVER_CHAINS);
+                if (ns >= S.cap_seeds) return leave(SC_OVER_SEEDS);
                 S.seeds[ns] = s;
                 Chain c;
                 c.pos = s.rbeg;
@@ -1231,6 +1245,7 @@ SC_HD int chain_seq(const IndexView &I, const pr_seed_opts &O, Scratch &S, int n
                     R.tpos = s.rbeg;
                     R.f_rbeg = R.l_rbeg = s.rbeg;
                     R.f_ql = R.l_ql = pack_ql(s);
+                    R.pad[0] = hs;
                     S.htab[hs].key = key[u];
                     S.htab[hs].r = nrg++;
                     S.cnx[ncv] = -1;
@@ -1260,7 +1275,10 @@ SC_HD int chain_seq(const IndexView &I, const pr_seed_opts &O, Scratch &S, int n
             }
         }
     }
-    for (int r = 0; r < nrg; ++r) flush_tail(S, S.rg[r]);
+    for (int r = 0; r < nrg; ++r) {
+        flush_tail(S, S.rg[r]);
+        if (clean_on_entry) S.htab[S.rg[r].pad[0]].key = -1;
+    }
     *n_cv = ncv;
     return 0;
 }
@@ -1270,9 +1288,11 @@ SC_HD int chain_seq(const IndexView &I, const pr_seed_opts &O, Scratch &S, int n
 // pos-ordered chains = a sort by (weight desc, pos, creation order = first seed's index)
 SC_HD void chain_flt(const pr_seed_opts &O, Scratch &S, int ncv, int *n_chains) {
     int nch = 0;
+    const bool keep_all = O.drop_ratio <= 0;
     for (int j = 0; j < ncv; ++j) {
         Chain c = S.cv[j];
         c.w = chain_weight(S, c);
+        if (keep_all) c.kept = 3;
         if (c.w >= O.min_chain_weight) S.ch[nch++] = c;
     }
     for (int i = 1; i < nch; ++i) {
@@ -1286,7 +1306,11 @@ SC_HD void chain_flt(const pr_seed_opts &O, Scratch &S, int ncv, int *n_chains) 
         }
         S.ch[j + 1] = v;
     }
-    if (nch > 0) {
+    // -D 0 (bwa-sr-1..6, bwa-mr-1): a chain ends with kept == 0 only through the drop test below,
+    // which no chain meets when drop_ratio <= 0 (weights are >= a seed's length > 0), and only
+    // kept == 0 is read downstream -- every chain kept (marked above, with its weight), no scan of
+    // the kept list (four to five dependent loads a test, chains x kept tests)
+    if (nch > 0 && !keep_all) {
         int nk = 1;
         S.kept[0] = 0;
         S.ch[0].kept = 3;

@@ -639,6 +639,7 @@ __device__ bool chain_flt_wave(const pr_seed_opts &O, seedc::Scratch &S, int ncv
     const int64_t ge_bytes = (int64_t)S.lmax * HB * 4;
     if ((int64_t)ncv * 36 > ge_bytes) return false;
     struct Key { int32_t nw, head; int64_t pos; };   // nw = -weight (INT32_MAX: filtered out)
+    const bool keep_all = O.drop_ratio <= 0;
     Key *key = reinterpret_cast<Key *>(S.ge);
     for (int j = lane; j < ncv; j += 64) {
         Chain &c = S.cv[j];
@@ -667,10 +668,18 @@ __device__ bool chain_flt_wave(const pr_seed_opts &O, seedc::Scratch &S, int ncv
                 rank += (nw < ki.nw || (nw == ki.nw && (ps < ki.pos || (ps == ki.pos && hd < ki.head)))) ? 1 : 0;
             }
         }
-        if (pass) S.ch[rank] = S.cv[i];
+        if (pass) {
+            Chain c = S.cv[i];
+            if (keep_all) c.kept = 3;
+            S.ch[rank] = c;
+        }
     }
     __threadfence_block();
     wave_sync_lds();
+    if (keep_all) {   // (seed_core.h chain_flt: no chain is dropped at -D 0, none scanned)
+        *n_chains = nch;
+        return true;
+    }
     // the sorted chains' query intervals and weights; the kept list's (KV) and its first marks (F)
     int4 *iv = reinterpret_cast<int4 *>(S.ge);
     int4 *kv = iv + nch;
@@ -890,6 +899,24 @@ __global__ void __launch_bounds__(64 * SEED_WAVES, SEED_MINB) seed_batch_kernel(
     // per lane: SMEM pass, re-seeding, -y seeds + sort, chaining, mem_chain_flt, filter + output
     unsigned long long lt[6] = {0ULL, 0ULL, 0ULL, 0ULL, 0ULL, 0ULL};
     unsigned long long ot[3] = {0ULL, 0ULL, 0ULL};   // occurrence table: starts, hits, count table
+    // The lazy kernel: the 64 slices' range tables cleared once, by the wave (two entries a lane a
+    // store, coalesced); from here every read frees the slots it claimed (seed_core.h chain_seq,
+    // Scratch::htab_clean) instead of clearing 1,024 entries for its ~35 ranges.  Per launch: the
+    // passes carve the same buffer with other capacities.  The eager kernel's reads clear their
+    // tables themselves (measured faster there, chain_seq).
+    constexpr bool HTAB_REUSE = LZ;
+    if (HTAB_REUSE) {
+        struct __attribute__((aligned(8))) Ent2 { seedc::RangeEnt a, b; };   // (the table is 8-byte aligned)
+        const seedc::Scratch S0 = seedc::carve(base, D.caps);
+        const int64_t off = reinterpret_cast<uint8_t *>(S0.htab) - base;
+        const Ent2 free2{{-1, -1}, {-1, -1}};
+        for (int rd = 0; rd < 64; ++rd) {
+            Ent2 *t = reinterpret_cast<Ent2 *>(base + (int64_t)rd * D.stride + off);
+            for (int k = lane; k < S0.hsize / 2; k += 64) t[k] = free2;   // (hsize: a power of two >= 64)
+        }
+        __threadfence_block();
+        wave_sync_lds();
+    }
     for (;;) {
         int b0 = 0;
         if (lane == 0) b0 = atomicAdd(D.next, 64);
@@ -930,6 +957,7 @@ __global__ void __launch_bounds__(64 * SEED_WAVES, SEED_MINB) seed_batch_kernel(
             const int64_t o = D.sr_off[i];
             const int len = (int)(D.sr_off[i + 1] - o);
             seedc::Scratch S = seedc::carve(base + (int64_t)lane * D.stride, D.caps);
+            S.htab_clean = HTAB_REUSE;
             int n = 0, err = my_err;
             if (len > 0 && !err)
                 err = seedc::map_after_occ<LZ>(D.V, D.O, S, D.sr_seq + o, len, i, D.out + (int64_t)(i - D.out0) * D.caps.out,
