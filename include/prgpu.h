@@ -440,6 +440,9 @@ int pr_seed_gpu_index_digest(pr_ctx *ctx, uint64_t *out6);
 int pr_seed_gpu_index_last_ms(pr_ctx *ctx, double *ms);
 /* seeds of the last pr_seed_gpu_map (those kept in HBM when out = NULL) */
 int pr_seed_gpu_seed_count(pr_ctx *ctx, int64_t *n);
+/* diagnostics (tests): the seeds of the last pr_seed_gpu_map / pr_seed_gpu_map_sampled as they
+ * lie in HBM (read order, chain order), copied to the host (pr_seed_tasks_free) */
+int pr_seed_gpu_seeds(pr_ctx *ctx, pr_seed_tasks *out);
 /* reads of the last pr_seed_gpu_map that outgrew pass 1's small scratch slices (64 reads per
  * wave, lane per read) and ran in pass 2 (one wave per read, the large slices) */
 int pr_seed_gpu_pass2_reads(pr_ctx *ctx, int64_t *n);
@@ -468,6 +471,14 @@ int pr_seed_gpu_pass2_ms(pr_ctx *ctx, double *ms);
 /* diagnostics (tests): the device path's core and capacities (its passes included) run on the host */
 int pr_seed_map_device_caps(const pr_seed_index *h, const pr_seed_opts *o, const uint8_t *sr_seq,
                             const int64_t *sr_off, int n_sr, int n_threads, pr_seed_tasks *out, int32_t *status);
+/* diagnostics (tests): pass 1 of the device path alone on the host, one scratch slice for every
+ * read in read order, no later pass: status[i] the read's SC_OVER_* flags (its seeds are in out only
+ * when 0).  budget: pass 1's hit budget per read for the lazy table of the finish options (0:
+ * none).  hits[i], lazy table only: the hits of the read's pool, or for a read flagged on hits the
+ * need it reports to the next pass (its eager table's size) */
+int pr_seed_map_device_pass1(const pr_seed_index *h, const pr_seed_opts *o, const uint8_t *sr_seq,
+                             const int64_t *sr_off, int n_sr, int budget, pr_seed_tasks *out, int32_t *status,
+                             int32_t *hits);
 
 /* ------------------------------------------------------------------ */
 /* one correction iteration on the device: SW -> assemble -> consensus  */

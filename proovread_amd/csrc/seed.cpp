@@ -721,6 +721,21 @@ extern "C" void pr_seed_tasks_free(pr_seed_tasks *t) {
     if (t) t->t = nullptr, t->n = 0;
 }
 
+// the device's 4-bit text (16 bases a word, SEP past the end, 8 padding words), so the lazy
+// table's 64-base text walks run on the host as on the device
+static std::vector<uint64_t> pack_text4(const seedc::IndexView &V) {
+    std::vector<uint64_t> text4((size_t)(V.n_text / 16 + 8), 0);
+    for (size_t w = 0; w < text4.size(); ++w) {
+        uint64_t v = 0;
+        for (int k = 0; k < 16; ++k) {
+            const int64_t x = (int64_t)w * 16 + k;
+            v |= (uint64_t)(x < V.n_text ? V.text[x] : SEP) << (4 * k);
+        }
+        text4[w] = v;
+    }
+    return text4;
+}
+
 // The device path's arithmetic on the host: seed_core.h with the device's fixed
 // scratch capacities (seedc::device_caps), so tests can check which reads the GPU
 // kernel flags and that every other read gets the host path's tasks.
@@ -735,17 +750,7 @@ extern "C" int pr_seed_map_device_caps(const pr_seed_index *h, const pr_seed_opt
     seedc::IndexView V = view_of(h->I);
     int qmax = 1;
     for (int i = 0; i < n_sr; ++i) qmax = std::max<int>(qmax, (int)(sr_off[i + 1] - sr_off[i]));
-    // the device's 4-bit text (16 bases a word, SEP past the end, 8 padding words), so the lazy
-    // table's 64-base text walks run here as on the device
-    std::vector<uint64_t> text4((size_t)(V.n_text / 16 + 8), 0);
-    for (size_t w = 0; w < text4.size(); ++w) {
-        uint64_t v = 0;
-        for (int k = 0; k < 16; ++k) {
-            const int64_t x = (int64_t)w * 16 + k;
-            v |= (uint64_t)(x < V.n_text ? V.text[x] : SEP) << (4 * k);
-        }
-        text4[w] = v;
-    }
+    const std::vector<uint64_t> text4 = pack_text4(V);
     V.text4 = text4.data();
     seedc::Caps caps = seedc::device_caps(qmax);   // (the output slots follow the longest read, as on the device)
     caps.hi = V.ksplit != nullptr;
@@ -801,5 +806,45 @@ extern "C" int pr_seed_map_device_caps(const pr_seed_index *h, const pr_seed_opt
     for (auto &r : res)
         for (auto &t : r.tasks) out->t[k++] = t;
     out->n = total;
+    return 0;
+}
+
+// Pass 1 of the device path alone on the host: its small slices (seedc::device_caps_small) and
+// table for these options, a hit budget per read as pass 1 sets it (0: none), one slab for every
+// read in read order, the range table cleared once and then left clean by every read, no later pass.
+extern "C" int pr_seed_map_device_pass1(const pr_seed_index *h, const pr_seed_opts *o, const uint8_t *sr_seq,
+                                        const int64_t *sr_off, int n_sr, int budget, pr_seed_tasks *out, int32_t *status,
+                                        int32_t *hits) {
+    if (!h || !o || !out || !status || !hits || n_sr < 0 || budget < 0 || (n_sr && (!sr_seq || !sr_off)))
+        return pr_set_error(PR_ERR_ARG, "null arg");
+    if (o->min_seed_len < KI) return pr_set_error(PR_ERR_UNSUPPORTED, "min seed length below the 12-mer index");
+    out->n = 0;
+    out->t = nullptr;
+    seedc::IndexView V = view_of(h->I);
+    int qmax = 1;
+    for (int i = 0; i < n_sr; ++i) qmax = std::max<int>(qmax, (int)(sr_off[i + 1] - sr_off[i]));
+    const std::vector<uint64_t> text4 = pack_text4(V);
+    V.text4 = text4.data();
+    seedc::Caps caps = seedc::device_caps_small(std::min(qmax, seedc::device_caps(qmax).lmax));
+    caps.hi = V.ksplit != nullptr;
+    caps.lazy = seedc::lazy_occ(*o) ? 1 : 0;
+    caps.budget = budget;
+    std::vector<uint64_t> slab((size_t)(seedc::scratch_bytes(caps) / 8 + 1), 0);
+    seedc::Scratch S = seedc::carve(reinterpret_cast<uint8_t *>(slab.data()), caps);
+    for (int k = 0; k < S.hsize; ++k) S.htab[k].key = -1;
+    S.htab_clean = true;
+    std::vector<pr_seed_task> buf((size_t)caps.out), all;
+    for (int i = 0; i < n_sr; ++i) {
+        const int len = (int)(sr_off[i + 1] - sr_off[i]);
+        int n = 0, err = 0;
+        if (len > 0) err = seedc::map_read(V, *o, S, sr_seq + sr_off[i], len, i, buf.data(), caps.out, &n);
+        status[i] = err;
+        hits[i] = !caps.lazy || len <= 0 || (err & seedc::SC_OVER_LEN) ? 0 : (err & seedc::SC_OVER_HITS) ? S.lz[2] : S.lz[0];
+        if (!err) all.insert(all.end(), buf.begin(), buf.begin() + n);
+    }
+    out->t = (pr_seed_task *)std::malloc(sizeof(pr_seed_task) * (all.empty() ? 1 : all.size()));
+    if (!out->t) return pr_set_error(PR_ERR_ARG, "out of host memory");
+    std::copy(all.begin(), all.end(), out->t);
+    out->n = (int64_t)all.size();
     return 0;
 }

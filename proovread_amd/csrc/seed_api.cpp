@@ -342,14 +342,21 @@ static int gather_ranges(pr_ctx *c, const int64_t *ranges, int n_ranges, int64_t
     HIPCHK(hipSetDevice(c->device));
     int rc = dst.ensure((size_t)off.back() + 1);
     if (rc) return rc;
+    // the ranges' bytes (SeqChunker's chunks: several hundred a task; runs of consecutive chunks
+    // merged) copied by one kernel, not one copy each
+    std::vector<int64_t> so, dn, ln;
     int64_t at = 0;
     for (int k = 0; k < n_ranges; ++k) {
         const int64_t b0 = c->ss_off[(size_t)ranges[2 * k]], b1 = c->ss_off[(size_t)ranges[2 * k + 1]];
-        if (b1 > b0)
-            HIPCHK(hipMemcpyAsync(dst.as<uint8_t>() + at, c->ls[LS_SRSEQ].as<uint8_t>() + b0, (size_t)(b1 - b0),
-                                  hipMemcpyDeviceToDevice, c->stream));
+        if (b1 > b0) {
+            if (!so.empty() && so.back() + ln.back() == b0) ln.back() += b1 - b0;
+            else so.push_back(b0), dn.push_back(at), ln.push_back(b1 - b0);
+        }
         at += b1 - b0;
     }
+    const int e = sr_gather_launch(c->ls[LS_SRSEQ].as<uint8_t>(), dst.as<uint8_t>(), so.data(), dn.data(), ln.data(),
+                                   (int64_t)so.size(), (void *)c->stream);
+    if (e) return set_error(PR_ERR_HIP, "short-read gather: %s", hipGetErrorString((hipError_t)e));
     return 0;
 }
 
@@ -378,6 +385,7 @@ struct SeedMap {   // one map call
     int64_t waves;             // pass 1's
     int64_t lanes2;            // pass 2's resident waves
     int64_t chunk;             // reads per chunk
+    int32_t budget;            // pass 1's hit budget per read (lazy table; 0: none)
     // results so far: seeds per read, status, prefix of the seeds, flagged reads and their flags
     std::vector<int32_t> nout, st;
     std::vector<int64_t> pre;
@@ -405,6 +413,12 @@ void map_plan(SeedMap &M, const pr_seed_opts *o, const int64_t *sr_off) {
     small.lazy = seedc::lazy_occ(*o) ? 1 : 0;
     if (const char *sc = getenv("PRGPU_SEED_SMALL"))   // tuning hook: hits,iv,mems,seeds,chains
         sscanf(sc, "%d,%d,%d,%d,%d", &small.hits, &small.iv, &small.mems, &small.seeds, &small.chains);
+    // pass 1's lanes run in lock-step, so a lazy-table read can be handed to the next pass once its
+    // pool would pass a budget below the slice's capacity, instead of holding its 63 neighbours up
+    // to the slice's last hit (seed_plan.h PASS1_LAZY_BUDGET: none by default, no measurable gain
+    // at configs[1]).  PRGPU_SEED_BUDGET: tuning hook, 0: none
+    M.budget = small.lazy ? seedp::PASS1_LAZY_BUDGET : 0;
+    if (const char *bu = getenv("PRGPU_SEED_BUDGET")) M.budget = small.lazy ? std::max(0, atoi(bu)) : 0;
     SeedDev &K = M.K;
     K = SeedDev{};
     K.V = c->seed_view;
@@ -417,15 +431,22 @@ void map_plan(SeedMap &M, const pr_seed_opts *o, const int64_t *sr_off) {
     (void)hipMemGetInfo(&fr, &tot);
     (void)hipGetLastError();
     // (PRGPU_SEED_BALANCE: seed_plan.h pass1_waves)
-    M.waves = seedp::pass1_waves(M.n_sr, c->n_cu, wpc ? atoi(wpc) : 16, getenv("PRGPU_SEED_BALANCE") != nullptr,
-                                 seedp::scratch_budget((int64_t)fr, (int64_t)M.D[SB_SCRATCH].cap), K.stride);
+    const int per_cu = wpc ? atoi(wpc) : 16;
+    // every resident wave's slices where the memory allows (seed_plan.h pass1_budget); a text
+    // beyond 2^32 positions (configs[3] ranks) keeps scratch_budget: there the device memory peaks
+    // within a few GB of the card later in the task (as index_build gives its sort buffers back)
+    const int64_t full = caps.hi ? 0 : (int64_t)c->n_cu * per_cu * 64 * K.stride;
+    M.waves = seedp::pass1_waves(M.n_sr, c->n_cu, per_cu, getenv("PRGPU_SEED_BALANCE") != nullptr,
+                                 seedp::pass1_budget((int64_t)fr, (int64_t)M.D[SB_SCRATCH].cap, full), K.stride);
     K.n_lanes = M.waves;
     M.lanes2 = (int64_t)c->n_cu * seed_slots_per_cu(c->seed_view.walk_nw);
     // reads are mapped in chunks whose output slabs (caps.out seeds per read) fit a budget
-    // (PRGPU_SEED_OUT_MB, default 8 GB; configs[1]'s 460k reads are one chunk); every chunk's
-    // seeds are compacted into the dense list before the next chunk reuses the slab
+    // (PRGPU_SEED_OUT_MB, default seed_plan.h out_budget: 8 to 16 GB; configs[1]'s 460k reads and
+    // its finish task's 914k are one chunk); every chunk's seeds are compacted into the dense
+    // list before the next chunk reuses the slab
     const char *ob = getenv("PRGPU_SEED_OUT_MB");
-    M.chunk = seedp::out_chunk((ob ? std::max<int64_t>(1, atoll(ob)) : 8192) << 20,
+    M.chunk = seedp::out_chunk(ob ? std::max<int64_t>(1, atoll(ob)) << 20
+                                  : seedp::out_budget((int64_t)fr, (int64_t)M.D[SB_OUT].cap),
                                (int64_t)caps.out * (int64_t)sizeof(pr_seed_task));
 }
 
@@ -473,8 +494,10 @@ int pass1(SeedMap &M, int64_t r0, int64_t r1, std::vector<int32_t> &redo, seedp:
     hipStream_t s = M.s;
     int rc;
     K.caps = M.small;
+    K.caps.budget = M.budget;   // (pass 1 only: pass 1b's slices are sized for what the flagged reads need)
     K.stride = seedc::scratch_bytes(M.small);
     K.n_lanes = M.waves;
+    K.batch = 64;
     K.scratch = D[SB_SCRATCH].as<uint8_t>();
     K.rlist = nullptr;
     K.n_list = 0;
@@ -513,13 +536,14 @@ int pass1(SeedMap &M, int64_t r0, int64_t r1, std::vector<int32_t> &redo, seedp:
 
 // One more pass over `reads` of the chunk: the list to SB_PRE, the dequeue counter zeroed, the
 // kernel (by_wave: one wave per read, seed_launch; else 64 reads per wave, seed_batch_launch)
-// over `lanes` slices of `caps`
+// over `lanes` slices of `caps` (by lane: lanes waves of `batch` slices each)
 int launch_pass(SeedMap &M, const char *name, bool by_wave, const seedc::Caps &caps, int64_t lanes,
-                const std::vector<int32_t> &reads) {
+                const std::vector<int32_t> &reads, int batch = 64) {
     SeedDev &K = M.K;
     K.caps = caps;
     K.stride = seedc::scratch_bytes(caps);
     K.n_lanes = lanes;
+    K.batch = batch;
     K.scratch = M.D[SB_SCRATCH].as<uint8_t>();
     K.rlist = M.D[SB_PRE].as<int32_t>();
     K.n_list = (int64_t)reads.size();
@@ -567,7 +591,15 @@ int pass1b(SeedMap &M, int64_t r0, int64_t r1, const seedp::Flagged &f, std::vec
         seedp::pass1b_run(p, f, M.small.hits, force, (int64_t)scr.cap, M.waves, M.lanes2, M.c->n_cu);
     if (r.mode == seedp::P1B_SKIP) return 0;
     const bool by_wave = r.mode == seedp::P1B_WAVE;
-    if ((rc = launch_pass(M, by_wave ? "pass 1b, waves" : "pass 1b", by_wave, by_wave ? p.cw : p.cb, by_wave ? r.ww : r.wb, redo)))
+    // lane per read with the lazy table: the flagged reads over all of pass 1's waves (the eager
+    // kernel keeps 64 a wave).  PRGPU_SEED_1B_BATCH: tuning hook, the reads a wave takes at a time
+    seedp::Pass1bBatch b{64, r.wb};
+    if (!by_wave && p.cb.lazy) {
+        const char *bb = getenv("PRGPU_SEED_1B_BATCH");
+        b = seedp::pass1b_batch(r, f.n, M.waves, (int64_t)scr.cap, p.sb, bb ? atoi(bb) : 0);
+    }
+    if ((rc = launch_pass(M, by_wave ? "pass 1b, waves" : "pass 1b", by_wave, by_wave ? p.cw : p.cb, by_wave ? r.ww : b.waves,
+                          redo, b.batch)))
         return rc;
     M.c->seed_pass_reads[by_wave ? 1 : 0] += (int64_t)redo.size();
     if (by_wave) p2caps = p.cw, p2_ran = true;
@@ -721,6 +753,21 @@ extern "C" int pr_seed_gpu_map_sampled(pr_ctx *c, const pr_seed_opts *o, const i
 extern "C" int pr_seed_gpu_seed_count(pr_ctx *c, int64_t *n) {
     if (!c || !n) return set_error(PR_ERR_ARG, "null arg");
     *n = c->seed_pre.empty() ? 0 : c->seed_pre.back();
+    return 0;
+}
+
+extern "C" int pr_seed_gpu_seeds(pr_ctx *c, pr_seed_tasks *out) {
+    if (!c || !out) return set_error(PR_ERR_ARG, "null arg");
+    out->n = 0, out->t = nullptr;
+    if (c->seed_pre.empty()) return set_error(PR_ERR_ARG, "no complete seed set on the device");
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t total = c->seed_pre.back();
+    out->t = (pr_seed_task *)std::malloc(sizeof(pr_seed_task) * (size_t)(total > 0 ? total : 1));
+    if (!out->t) return set_error(PR_ERR_ARG, "out of host memory");
+    int rc;
+    if (total && (rc = download(out->t, c->sd[SB_DENSE], (size_t)total, c->stream))) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    out->n = total;
     return 0;
 }
 

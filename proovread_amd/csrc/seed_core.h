@@ -163,6 +163,7 @@ struct Scratch {
     uint8_t *ready;                            // [lmax + 1] start materialized
     uint64_t *q4w;                             // [lmax / 16 + 4] the read 16 bases per word (4 bits each), or null
     int32_t *lz;                               // [4] pool fill, SC_OVER_* flags, hits the read would need
+    int32_t lim_hits;                          // the pool's limit: cap_hits, or the pass's budget below it (Caps.budget)
     // set by the owner of the scratch: every key of htab is free between reads (the owner cleared
     // it once; chain_seq then frees the slots a read claimed instead of clearing the table)
     bool htab_clean;
@@ -270,6 +271,8 @@ constexpr int LC_N = lc_off(LC_MAX + 1);   // 4 + 16 + ... + 4^LC_MAX
 
 template <bool LZ> struct OccB;
 SC_HD void materialize(const OccB<true> &occ, int a);
+template <class OccT> struct occ_lazy { static constexpr bool value = false; };
+template <> struct occ_lazy<OccB<true>> { static constexpr bool value = true; };
 
 // The occurrence counts of read q's substrings.  LZ: the lazy table (Scratch.hend), a start
 // materialized on first use; the eager table's code (LZ = false) has no trace of it.
@@ -490,7 +493,9 @@ SC_HD int hit_ml(const IndexView &I, const Scratch &S, const uint8_t *q, int len
 
 // The lazy table's start a (Scratch.hend): its hits appended to the read's pool with their match
 // lengths and coordinates, its count row and R_1 .. R_RK -- the values the eager table holds for
-// it.  A pool that would overflow flags the read (lz[1]) and records the hits it needs (lz[2]).
+// it.  A pool that would pass its limit (the slice's capacity, or pass 1's budget below it) flags
+// the read (lz[1]) and records the hits it needs (lz[2]): its eager table, the sum of its starts'
+// 12-mer counts, which no lazy pool of the read exceeds -- the next pass sizes its slices from it.
 #if defined(__HIPCC__)
 __attribute__((noinline))   // (out of line: the eager table's kernels only test S.hend)
 #endif
@@ -512,9 +517,16 @@ SC_HD void materialize(const OccLazy &occ, int a) {
     if (code >= 0) {
         const uint64_t r0 = I.koff[code], r1 = I.koff[code + 1];
         const int64_t need = (int64_t)beg + (int64_t)(r1 - r0);
-        if (need > S.cap_hits) {
+        if (need > S.lim_hits) {
+            if (!(S.lz[1] & SC_OVER_HITS)) {
+                int64_t all = 0;
+                for (int x = 0; x + KI <= len; ++x) {
+                    const int32_t cx = S.codes[x];
+                    if (cx >= 0) all += (int64_t)(I.koff[cx + 1] - I.koff[cx]);
+                }
+                S.lz[2] = (int32_t)(all < (int64_t)1 << 30 ? all : (int64_t)1 << 30);
+            }
             S.lz[1] |= SC_OVER_HITS;
-            S.lz[2] = (int32_t)(need < (int64_t)1 << 30 ? need : (int64_t)1 << 30);
         } else {
             n = (int32_t)(r1 - r0);
             const uint64_t qe = S.qext[a];
@@ -837,6 +849,13 @@ SC_HD int collect_intv(const OccT &occ, Scratch &S, const pr_seed_opts &O, const
     unsigned long long t_last = ticks ? __builtin_amdgcn_s_memrealtime() : 0ULL;
 #endif
     int nm = 0, n1 = 0;
+    // the lazy table's pool passed its limit: the counts from here on are not valid and the read
+    // is mapped again by the next pass, so every round below ends at once (before chain_seq:
+    // no range-table slot is claimed)
+    auto over = [&]() -> bool {
+        if constexpr (occ_lazy<OccT>::value) return S.lz[1] != 0;
+        else return false;
+    };
     auto push = [&](const Iv &v) {
         if (nm >= S.cap_mems) {
             err |= SC_OVER_MEMS;
@@ -844,7 +863,7 @@ SC_HD int collect_intv(const OccT &occ, Scratch &S, const pr_seed_opts &O, const
         }
         S.mems[nm++] = v;
     };
-    for (int x = 0; x < len && !err;) {
+    for (int x = 0; x < len && !err && !over();) {
         if (q[x] < 4) {
             x = smem1(occ, S, q, len, x, 1, S.m1, n1, err);
             for (int k = 0; k < n1; ++k)
@@ -856,7 +875,7 @@ SC_HD int collect_intv(const OccT &occ, Scratch &S, const pr_seed_opts &O, const
     SC_TICK(0);
     const int split_len = (int)(O.min_seed_len * O.split_factor + .499);
     const int nfirst = nm;
-    for (int k = 0; k < nfirst && !err; ++k) {
+    for (int k = 0; k < nfirst && !err && !over(); ++k) {
         const Iv p = S.mems[k];
         if (p.end - p.start < split_len || p.occ > O.split_width) continue;
         smem1(occ, S, q, len, (p.start + p.end) >> 1, p.occ + 1, S.m1, n1, err);
@@ -865,7 +884,7 @@ SC_HD int collect_intv(const OccT &occ, Scratch &S, const pr_seed_opts &O, const
     }
     SC_TICK(1);
     if (O.max_mem_intv > 0) {
-        for (int x = 0; x < len && !err;) {
+        for (int x = 0; x < len && !err && !over();) {
             if (q[x] < 4) {
                 Iv m;
                 x = seed_strategy1(occ, q, len, x, O.min_seed_len, O.max_mem_intv, m);
@@ -875,6 +894,7 @@ SC_HD int collect_intv(const OccT &occ, Scratch &S, const pr_seed_opts &O, const
             }
         }
     }
+    if (over()) return nm;
     // stable sort by (start, end): a counting sort by start (into the seed pool, free until
     // mem_chain; the counts in `codes`, which nothing reads after the occurrence lookups; any
     // input order -- the SMEM pass and the -y round come out sorted by start, the re-seeding round
@@ -1486,6 +1506,8 @@ struct Caps {
     int32_t nopos;   // no hit positions (hpos / hhi): the device's tables keep only the chaining's
                      // coordinates (hfr); the host's build_occ follows diagonals through hpos
     int32_t lazy;    // the lazy occurrence table (Scratch.hend / ready / q4w / lz)
+    int32_t budget;  // lazy table: a read whose pool would pass this many hits is flagged SC_OVER_HITS as at
+                     // `hits` (pass 1: its lanes run in lock-step, so a heavy read is handed on early); 0: none
 };
 // output slots per read (the seeds of its kept chains): 384 for short reads, 2 per base for
 // the mr modes' 300-1000 bp reads (~300 seeds per 600 bp read at 15x long-read coverage)
@@ -1583,6 +1605,7 @@ SC_HD Scratch carve(uint8_t *p, const Caps &c) {
     S.hpos = c.nopos ? nullptr : (uint32_t *)take(4 * (int64_t)c.hits);
     S.hml = (uint16_t *)take(2 * (int64_t)c.hits);
     S.cap_hits = c.hits;
+    S.lim_hits = c.lazy && c.budget > 0 && c.budget < c.hits ? c.budget : c.hits;
     S.mems = (Iv *)take((int64_t)sizeof(Iv) * c.mems);
     S.cap_mems = c.mems;
     S.m1 = (Iv *)take((int64_t)sizeof(Iv) * c.iv);

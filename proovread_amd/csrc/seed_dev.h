@@ -29,6 +29,7 @@ struct SeedDev {
     int16_t *dp;               // pass 1: per wave 2 x 201 x 64 int16 (mem_flt_chained_seeds rows, lane-interleaved)
     const int32_t *rlist;      // pass 2: the reads to map (n_list of them); null: 0 .. n_list
     int64_t n_list;
+    int32_t batch;             // lazy kernel: reads a wave dequeues at a time = slices per wave (1..64; pass 1: 64)
 };
 
 int seed_launch(const SeedDev &D, void *stream);         // pass 2: one wave per read of rlist
@@ -39,6 +40,11 @@ int seed_batch_launch(const SeedDev &D, void *stream);   // pass 1: 64 reads per
 size_t seed_order_bytes(int64_t n);
 int seed_order_launch(const SeedDev &D, int64_t r0, int64_t n, void *buf, int32_t **order, void *stream);
 // resident waves per CU of the seeding kernel (= scratch slots per CU)
+// the resident short reads' byte ranges gathered into one buffer: dst[d_off[k] ..) = src[s_off[k] ..)
+// for len[k] bytes, k < n (host arrays; any alignment), one kernel per GATHER_RANGES ranges
+constexpr int GATHER_RANGES = 112;
+int sr_gather_launch(const uint8_t *src, uint8_t *dst, const int64_t *s_off, const int64_t *d_off, const int64_t *len,
+                     int64_t n, void *stream);
 int seed_slots_per_cu(int walk_nw);   // pass 2's resident waves per CU (seed_wave_kernel<walk_nw>)
 // dense task list: out[pre[i] + j] = slots[i * cap + j] for j < n_out[i]
 int seed_compact_launch(const pr_seed_task *slots, const int32_t *n_out, const int64_t *pre, int64_t n_sr, int cap,

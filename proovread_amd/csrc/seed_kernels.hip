@@ -893,7 +893,12 @@ __global__ void __launch_bounds__(64 * SEED_WAVES, SEED_MINB) seed_batch_kernel(
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t slot = (int64_t)blockIdx.x * SEED_WAVES + wv;
     if (slot >= D.n_lanes) return;
-    uint8_t *base = D.scratch + slot * 64 * D.stride;
+    // reads per dequeue = the wave's slices.  The lazy kernel takes it from the launch (pass 1b
+    // spreads its few reads over every resident wave, seed_plan.h pass1b_batch); the eager
+    // kernel's is the constant it always was
+    int batch = 64;
+    if constexpr (LZ) batch = D.batch;
+    uint8_t *base = D.scratch + slot * batch * D.stride;
     int32_t *ho = hoff_lds[wv];
     unsigned long long pt[2] = {0ULL, 0ULL};   // wave wall-clock: occurrence tables, lane work
     // per lane: SMEM pass, re-seeding, -y seeds + sort, chaining, mem_chain_flt, filter + output
@@ -910,7 +915,7 @@ __global__ void __launch_bounds__(64 * SEED_WAVES, SEED_MINB) seed_batch_kernel(
         const seedc::Scratch S0 = seedc::carve(base, D.caps);
         const int64_t off = reinterpret_cast<uint8_t *>(S0.htab) - base;
         const Ent2 free2{{-1, -1}, {-1, -1}};
-        for (int rd = 0; rd < 64; ++rd) {
+        for (int rd = 0; rd < batch; ++rd) {
             Ent2 *t = reinterpret_cast<Ent2 *>(base + (int64_t)rd * D.stride + off);
             for (int k = lane; k < S0.hsize / 2; k += 64) t[k] = free2;   // (hsize: a power of two >= 64)
         }
@@ -919,7 +924,7 @@ __global__ void __launch_bounds__(64 * SEED_WAVES, SEED_MINB) seed_batch_kernel(
     }
     for (;;) {
         int b0 = 0;
-        if (lane == 0) b0 = atomicAdd(D.next, 64);
+        if (lane == 0) b0 = atomicAdd(D.next, batch);
         b0 = __shfl(b0, 0, 64);
         const int64_t nlim = D.rlist ? D.n_list : D.n_sr;   // rlist: the reads of a retry pass
         if (b0 >= nlim) {   // every wave reaches this: the grid drains
@@ -938,7 +943,7 @@ __global__ void __launch_bounds__(64 * SEED_WAVES, SEED_MINB) seed_batch_kernel(
         }
         const unsigned long long t0 = D.prof ? wall_clock64() : 0ULL;
         int my_err = 0, my_hits = 0;
-        const int nb = (int)(nlim - b0 < 64 ? nlim - b0 : 64);
+        const int nb = (int)(nlim - b0 < batch ? nlim - b0 : batch);
         for (int rd = 0; rd < nb; ++rd) {
             const int i = D.rlist ? D.rlist[b0 + rd] : b0 + rd;
             const int64_t o = D.sr_off[i];
@@ -966,7 +971,7 @@ __global__ void __launch_bounds__(64 * SEED_WAVES, SEED_MINB) seed_batch_kernel(
             // a read whose hit table overflowed reports the hits it needs (the retry pass sizes
             // its slices from them: texts of 1 - 3 Gb give ~20-50 k hits per 150 bp read)
             D.n_out[i] = (my_err & seedc::SC_OVER_HITS) ? -my_hits
-                         : (LZ && (err & seedc::SC_OVER_HITS)) ? -S.lz[2]   // (the lazy pool's need)
+                         : (LZ && (err & seedc::SC_OVER_HITS)) ? -S.lz[2]   // (the lazy table's need: the eager size)
                                                                         : (err ? 0 : n);
             D.status[i] = err;
         }
@@ -1034,6 +1039,53 @@ int seed_order_launch(const SeedDev &D, int64_t r0, int64_t n, void *buf, int32_
     return 0;
 }
 
+// The short reads' byte ranges into one buffer (sr_gather_launch): block (x, y) copies tiles x,
+// x + gridDim.x, ... of range y.  Each tile: bytes up to the destination's next 16-byte boundary,
+// then 16 bytes a lane (the destination aligned, the source as it falls), then the last bytes.
+struct GatherArgs {
+    int64_t s_off[GATHER_RANGES], d_off[GATHER_RANGES], len[GATHER_RANGES];
+};
+constexpr int64_t GATHER_TILE = 64 << 10;
+__global__ void __launch_bounds__(256) sr_gather_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, GatherArgs A) {
+    const int64_t n = A.len[blockIdx.y];
+    const uint8_t *s = src + A.s_off[blockIdx.y];
+    uint8_t *d = dst + A.d_off[blockIdx.y];
+    // tiles start at the destination's 16-byte boundaries after the range's unaligned head
+    const int64_t head = std::min<int64_t>(n, (int64_t)((16 - (reinterpret_cast<uintptr_t>(d) & 15)) & 15));
+    if (blockIdx.x == 0)
+        for (int64_t k = threadIdx.x; k < head; k += blockDim.x) d[k] = s[k];
+    const int64_t body = (n - head) & ~(int64_t)15;
+    for (int64_t t0 = (int64_t)blockIdx.x * GATHER_TILE; t0 < body; t0 += (int64_t)gridDim.x * GATHER_TILE) {
+        const int64_t t1 = std::min<int64_t>(body, t0 + GATHER_TILE);
+        for (int64_t k = t0 + (int64_t)threadIdx.x * 16; k < t1; k += (int64_t)blockDim.x * 16) {
+            uint4 v;
+            __builtin_memcpy(&v, s + head + k, 16);
+            *reinterpret_cast<uint4 *>(d + head + k) = v;
+        }
+    }
+    if (blockIdx.x == 0)
+        for (int64_t k = head + body + threadIdx.x; k < n; k += blockDim.x) d[k] = s[k];
+}
+int sr_gather_launch(const uint8_t *src, uint8_t *dst, const int64_t *s_off, const int64_t *d_off, const int64_t *len,
+                     int64_t n, void *stream) {
+    for (int64_t k0 = 0; k0 < n; k0 += GATHER_RANGES) {
+        const int m = (int)std::min<int64_t>(GATHER_RANGES, n - k0);
+        GatherArgs A{};
+        int64_t lmax = 0;
+        for (int k = 0; k < m; ++k) {
+            A.s_off[k] = s_off[k0 + k];
+            A.d_off[k] = d_off[k0 + k];
+            A.len[k] = len[k0 + k];
+            lmax = std::max(lmax, A.len[k]);
+        }
+        const int64_t tiles = std::max<int64_t>(1, std::min<int64_t>(256, (lmax + GATHER_TILE - 1) / GATHER_TILE));
+        hipLaunchKernelGGL(sr_gather_kernel, dim3((unsigned)tiles, (unsigned)m), dim3(256), 0, (hipStream_t)stream, src, dst, A);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+    }
+    return 0;
+}
+
 int seed_slots_per_cu(int walk_nw) {
     int nb = 0;
     const hipError_t e = walk_nw == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, seed_wave_kernel<1>, 64 * SEED_WAVES, 0)
@@ -1055,6 +1107,7 @@ int seed_launch(const SeedDev &D, void *stream) {
 
 int seed_batch_launch(const SeedDev &D, void *stream) {
     if (D.n_sr <= 0) return 0;
+    if (D.caps.lazy && (D.batch < 1 || D.batch > 64)) return (int)hipErrorInvalidValue;
     const int64_t blocks = (D.n_lanes + SEED_WAVES - 1) / SEED_WAVES;
     if (D.caps.lazy)
         hipLaunchKernelGGL(seed_batch_kernel<true>, dim3((unsigned)blocks), dim3(64 * SEED_WAVES), 0, (hipStream_t)stream, D);

@@ -24,6 +24,15 @@ inline int64_t scratch_budget(int64_t free_bytes, int64_t have) {
 // budget can lie above the memory a crowded device has, and a failed allocation ends the map.
 inline bool scratch_growth_fits(int64_t want, int64_t free_bytes, int64_t have) { return want <= (free_bytes + have) / 2; }
 
+// Pass 1's budget: scratch_budget, or what every resident wave's slices need (`full`: 16 waves per
+// CU x 64 slices) where that is more, within the 40 GB ceiling and a quarter of the free memory.
+// Inside the correction loop the other stages hold ~130 GB, 15 % of the rest is under the 24 GB
+// floor, and the floor holds ~3,700 of configs[1]'s 4,096 waves (they need 26.6 to 28 GB): the
+// lane phase is latency-bound and lost ~3 % per launch to the missing waves.
+inline int64_t pass1_budget(int64_t free_bytes, int64_t have, int64_t full) {
+    const int64_t b = scratch_budget(free_bytes, have);
+    return full > b && full <= ((int64_t)40 << 30) && full <= (free_bytes + have) / 4 ? full : b;
+}
 // waves of pass 1 that the budget holds (64 slices of `stride` bytes each), a wave per CU at least
 inline int64_t pass1_wave_cap(int n_cu, int64_t budget, int64_t stride) {
     return std::max<int64_t>(n_cu, budget / (64 * stride));
@@ -44,6 +53,21 @@ inline int64_t pass1_waves(int64_t n_sr, int n_cu, int waves_per_cu, bool balanc
     return std::min(waves, pass1_wave_cap(n_cu, budget, stride));
 }
 
+// Pass 1's hit budget per read when the table is lazy (seed_api.cpp map_plan), 0: none.  Measured at
+// configs[1]'s finish task: 1536 - 2048 hits flag 404 - 153 of 914 k reads and gain
+// about 1 ms of 93, within the runs' spread; 1024 and below cost more in the next pass than pass 1
+// saves.  So none by default; PRGPU_SEED_BUDGET sets one.
+constexpr int32_t PASS1_LAZY_BUDGET = 0;
+
+// The budget of a chunk's output slabs: a tenth of the free device memory, between 8 and 16 GB.
+// A chunk is a pass-1 launch with its own drain (the last batches run on a mostly idle device),
+// status download and compaction, so a task should be one chunk where the memory allows: the
+// finish task's 914 k reads of configs[1] need 14 GB and ran as two launches under the fixed 8 GB
+// (seeding 107 -> 94 ms); a crowded device keeps the 8 GB.
+// have: the bytes SB_OUT already holds
+inline int64_t out_budget(int64_t free_bytes, int64_t have) {
+    return std::min<int64_t>((int64_t)16 << 30, std::max<int64_t>((int64_t)8 << 30, (free_bytes + have) / 10));
+}
 // reads per chunk: their output slabs (slot_bytes a read) within out_budget, a multiple of 64
 inline int64_t out_chunk(int64_t out_budget, int64_t slot_bytes) {
     return std::max<int64_t>(64, out_budget / slot_bytes / 64 * 64);
@@ -134,6 +158,29 @@ inline Pass1bRun pass1b_run(const Pass1bCaps &p, const Flagged &f, int32_t small
     r.ww = std::min<int64_t>(std::min<int64_t>(lanes2, f.n), scratch_cap / p.sw);
     r.mode = !pass1b_wanted(f) ? P1B_SKIP : r.by_wave && r.ww >= n_cu ? P1B_WAVE : r.wb >= n_cu ? P1B_LANE : P1B_SKIP;
     return r;
+}
+
+// Pass 1b, lane per read, of a lazy-table task: the reads a wave dequeues at a time (= its slices)
+// and the waves.  The flagged reads of a finish task are a heavy minority (a few ten thousand of
+// ~900 k): at 64 a wave they fill a few hundred of pass 1's waves and the launch is as long as
+// one wave's 64 occurrence tables and its slowest lane on a mostly idle device.  So one batch
+// per wave over as many waves as pass 1 ran: n reads -> ceil(n / waves) a wave.  Waves beyond
+// the scratch's room (batch slices each) are dropped; the rest then dequeue more than once.
+// r: pass1b_run's result (wb: the waves at 64 reads each, the floor when nothing else fits);
+// force: PRGPU_SEED_1B_BATCH (0: none)
+struct Pass1bBatch {
+    int32_t batch;   // 1 .. 64
+    int64_t waves;
+};
+inline Pass1bBatch pass1b_batch(const Pass1bRun &r, int64_t n_flagged, int64_t waves, int64_t scratch_cap, int64_t sb,
+                                int force) {
+    Pass1bBatch b;
+    waves = std::max<int64_t>(waves, 1);
+    const int64_t per = force > 0 ? force : (n_flagged + waves - 1) / waves;
+    b.batch = (int32_t)std::min<int64_t>(64, std::max<int64_t>(1, per));
+    b.waves = std::min<int64_t>(std::min<int64_t>((n_flagged + b.batch - 1) / b.batch, waves), scratch_cap / (b.batch * sb));
+    if (b.waves < 1) b.batch = 64, b.waves = r.wb;   // (at 64 a wave the result is wb itself)
+    return b;
 }
 
 }  // namespace seedp

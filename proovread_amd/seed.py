@@ -143,6 +143,23 @@ class SeedIndex:
                    "pr_seed_map_device_caps")
         return self._take(out), st[:len(sr_off) - 1]
 
+    def map_device_pass1(self, sr_seq: np.ndarray, sr_off: np.ndarray, opts: SeedOpts | None = None, budget: int = 0):
+        """Pass 1 of the GPU path alone on the host, one scratch slice for all reads in order
+        (pr_seed_map_device_pass1) -> (tasks of the unflagged reads, status per read, hits per read:
+        the lazy pool's fill, or the need a read flagged on hits reports)."""
+        opts = opts or default_opts()
+        sr_seq = np.ascontiguousarray(sr_seq, np.uint8)
+        sr_off = np.ascontiguousarray(sr_off, np.int64)
+        n = len(sr_off) - 1
+        st, hits = np.zeros(max(1, n), np.int32), np.zeros(max(1, n), np.int32)
+        out = SeedTasks()
+        self.L.pr_seed_map_device_pass1.argtypes = [C.c_void_p, C.POINTER(SeedOpts), C.c_void_p, C.c_void_p, C.c_int,
+                                                    C.c_int, C.POINTER(SeedTasks), C.c_void_p, C.c_void_p]
+        _abi.check(self.L.pr_seed_map_device_pass1(self.h, C.byref(opts), sr_seq.ctypes.data, sr_off.ctypes.data, n,
+                                                   budget, C.byref(out), st.ctypes.data, hits.ctypes.data),
+                   "pr_seed_map_device_pass1")
+        return self._take(out), st[:n], hits[:n]
+
     def to_gpu(self, ctx: "_abi.Context"):
         """Copy the index into the context's HBM (pr_seed_gpu_upload)."""
         _abi.check(self.L.pr_seed_gpu_upload(ctx.h, self.h), "pr_seed_gpu_upload")
