@@ -14,8 +14,6 @@
 #include "bam_core.h"
 #include "bam_dev.h"
 
-double bam_perl_number(const char *s, const char *e);   // bam_codec.cpp
-
 using namespace prgpu::bam;
 
 namespace {

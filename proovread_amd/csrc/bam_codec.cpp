@@ -21,8 +21,8 @@
 #include <vector>
 
 #include "../../include/prgpu.h"
-
-int pr_set_error(int code, const char *msg);
+#include "bam_codec.h"
+#include "err.h"
 
 namespace {
 

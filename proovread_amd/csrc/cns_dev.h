@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cns_plan.h"
+
 namespace prgpu {
 
 // negative PR_ERR_* codes (include/prgpu.h) used inside kernels
@@ -78,7 +80,7 @@ struct CnsDev {
     int32_t *retry_n;    // [1]
     int force_large;     // diagnostics: every read through the large geometry (PRGPU_CNS_LARGE)
     int debug;           // timing ablations only (PRGPU_CNS_DEBUG; outputs invalid when set)
-    unsigned long long *prof;  // [CNS_NPHASE] summed wall-clock ticks per phase (may be null)
+    unsigned long long *prof;  // [CNS_NPHASE, cns_plan.h] summed wall-clock ticks per phase (may be null)
     // outputs
     const int64_t *out_off;  // [n_lr+1]
     const int64_t *chim_off; // [n_lr+1]
@@ -99,8 +101,5 @@ constexpr int CNS_THREADS = 256;
 constexpr int CHIM_MAXCOLS = 128;
 constexpr int CHIM_TCAP = 256;
 constexpr int CHIM_CL = 8;   // insertion states a column's chimera entry list holds (more: the table scan)
-// per-phase wall-clock ticks: prep, binning, state table, scatter, argmax+write, cigar, chimera,
-// idle; scatter detail: zero+ignore, group select, staging, walks; counts: groups, items, windows
-constexpr int CNS_NPHASE = 24;
 
 }  // namespace prgpu

@@ -19,11 +19,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/prgpu.h"
-
-hipStream_t ctx_stream(pr_ctx *c);
-int ctx_device(pr_ctx *c);
-int pr_set_error(int code, const char *msg);
+#include "ctx.h"
 
 static_assert(PR_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "unique id size");
 constexpr int64_t P2P_PIECE = (int64_t)1 << 28;   // bytes per ncclSend / ncclRecv
@@ -79,26 +75,16 @@ struct pr_comm {
     size_t stage_cap = 0;
 };
 
-#define HIPCHK(x)                                                                 \
-    do {                                                                          \
-        hipError_t e_ = (x);                                                      \
-        if (e_ != hipSuccess) {                                                   \
-            std::string m_ = std::string(#x) + " failed: " + hipGetErrorString(e_); \
-            return pr_set_error(PR_ERR_HIP, m_.c_str());                          \
-        }                                                                         \
-    } while (0)
-#define NCCLCHK(x)                                                                  \
-    do {                                                                            \
-        ncclResult_t r_ = (x);                                                      \
-        if (r_ != ncclSuccess) {                                                    \
-            std::string m_ = std::string(#x) + " failed: " + ncclGetErrorString(r_); \
-            return pr_set_error(PR_ERR_HIP, m_.c_str());                            \
-        }                                                                           \
+#define NCCLCHK(x)                                                                         \
+    do {                                                                                   \
+        ncclResult_t r_ = (x);                                                             \
+        if (r_ != ncclSuccess)                                                             \
+            return set_error(PR_ERR_HIP, "%s failed: %s", #x, ncclGetErrorString(r_));     \
     } while (0)
 
 // (the staging buffer lives on the context's device, whatever the calling thread's current one)
 static int stage(pr_comm *c, size_t bytes) {
-    HIPCHK(hipSetDevice(ctx_device(c->ctx)));
+    HIPCHK(hipSetDevice(c->ctx->device));
     if (c->stage && c->stage_cap >= bytes) return 0;
     if (c->stage) (void)hipFree(c->stage);
     c->stage = nullptr;
@@ -129,7 +115,7 @@ extern "C" int pr_comm_unique_id(uint8_t *id) {
 extern "C" int pr_comm_init(pr_ctx *ctx, int world, int rank, const uint8_t *id, pr_comm **out) {
     if (!ctx || !out || !id) return pr_set_error(PR_ERR_ARG, "null arg");
     if (world < 1 || rank < 0 || rank >= world) return pr_set_error(PR_ERR_ARG, "bad rank / world size");
-    HIPCHK(hipSetDevice(ctx_device(ctx)));
+    HIPCHK(hipSetDevice(ctx->device));
     ncclUniqueId u;
     std::memcpy(u.internal, id, NCCL_UNIQUE_ID_BYTES);
     pr_comm *c = new pr_comm();
@@ -174,8 +160,8 @@ extern "C" int pr_comm_init_local(pr_ctx *ctx, pr_comm_group *g, int rank, pr_co
 
 // the in-process group's collectives (synchronous: each rank's stream is drained first)
 static int local_sync(pr_comm *c) {
-    HIPCHK(hipSetDevice(ctx_device(c->ctx)));
-    HIPCHK(hipStreamSynchronize(ctx_stream(c->ctx)));
+    HIPCHK(hipSetDevice(c->ctx->device));
+    HIPCHK(hipStreamSynchronize(c->ctx->stream));
     return 0;
 }
 
@@ -245,19 +231,19 @@ static int local_pull(pr_comm *c, const void *send, const int64_t *send_counts, 
             break;
         }
         if (n && hipMemcpyAsync((uint8_t *)recv + o, (const uint8_t *)p.send + off, (size_t)n, hipMemcpyDefault,
-                                ctx_stream(c->ctx)) != hipSuccess)
+                                c->ctx->stream) != hipSuccess)
             rc = pr_set_error(PR_ERR_HIP, "in-process all-to-all copy failed");
         o += n;
     }
-    if (!rc && hipStreamSynchronize(ctx_stream(c->ctx)) != hipSuccess) rc = pr_set_error(PR_ERR_HIP, "stream sync");
+    if (!rc && hipStreamSynchronize(c->ctx->stream) != hipSuccess) rc = pr_set_error(PR_ERR_HIP, "stream sync");
     if (!g->barrier()) return rc ? rc : group_aborted();   // every rank has finished reading the send buffers
     return rc;
 }
 
 extern "C" void pr_comm_destroy(pr_comm *c) {
     if (!c) return;
-    (void)hipSetDevice(ctx_device(c->ctx));
-    (void)hipStreamSynchronize(ctx_stream(c->ctx));
+    (void)hipSetDevice(c->ctx->device);
+    (void)hipStreamSynchronize(c->ctx->stream);
     if (c->nc) (void)ncclCommDestroy(c->nc);   // (an in-process group is the caller's: pr_comm_group_destroy)
     if (c->stage) (void)hipFree(c->stage);
     delete c;
@@ -269,8 +255,8 @@ extern "C" int pr_comm_allreduce_dev(pr_comm *c, const void *dev_in, void *dev_o
     const ncclDataType_t t = dtype_of(dtype, &sz);
     const ncclRedOp_t o = op == PR_RED_MAX ? ncclMax : (op == PR_RED_MIN ? ncclMin : ncclSum);
     if (c->grp) return local_allreduce_dev(c, dev_in, dev_out, n, dtype, op);
-    HIPCHK(hipSetDevice(ctx_device(c->ctx)));
-    NCCLCHK(ncclAllReduce(dev_in, dev_out, (size_t)n, t, o, c->nc, ctx_stream(c->ctx)));
+    HIPCHK(hipSetDevice(c->ctx->device));
+    NCCLCHK(ncclAllReduce(dev_in, dev_out, (size_t)n, t, o, c->nc, c->ctx->stream));
     return 0;
 }
 
@@ -282,8 +268,8 @@ extern "C" int pr_comm_allreduce_host(pr_comm *c, void *buf, int64_t n, int dtyp
     if (c->grp) return local_allreduce_host(c, buf, n, dtype, op);
     int rc = stage(c, bytes);
     if (rc) return rc;
-    hipStream_t s = ctx_stream(c->ctx);
-    HIPCHK(hipSetDevice(ctx_device(c->ctx)));
+    hipStream_t s = c->ctx->stream;
+    HIPCHK(hipSetDevice(c->ctx->device));
     HIPCHK(hipMemcpyAsync(c->stage, buf, bytes, hipMemcpyHostToDevice, s));
     if ((rc = pr_comm_allreduce_dev(c, c->stage, c->stage, n, dtype, op))) return rc;
     HIPCHK(hipMemcpyAsync(buf, c->stage, bytes, hipMemcpyDeviceToHost, s));
@@ -327,10 +313,10 @@ extern "C" int pr_comm_allgatherv_host(pr_comm *c, const uint8_t *send, int64_t 
     // in pieces of at most P2P_PIECE bytes per rank (one staging area of world + 1 pieces)
     const int64_t piece = std::min<int64_t>((cap + 255) & ~(int64_t)255, P2P_PIECE);
     if ((rc = stage(c, (size_t)piece * (size_t)(W + 1)))) return rc;
-    hipStream_t s = ctx_stream(c->ctx);
+    hipStream_t s = c->ctx->stream;
     uint8_t *mine = (uint8_t *)c->stage + (size_t)piece * (size_t)W;
     uint8_t *all = (uint8_t *)c->stage;
-    HIPCHK(hipSetDevice(ctx_device(c->ctx)));
+    HIPCHK(hipSetDevice(c->ctx->device));
     std::vector<int64_t> o((size_t)W + 1, 0);
     for (int r = 0; r < W; ++r) o[(size_t)r + 1] = o[(size_t)r] + sz[(size_t)r];
     for (int64_t k = 0; k < cap; k += piece) {
@@ -364,9 +350,9 @@ extern "C" int pr_comm_alltoallv_host(pr_comm *c, const uint8_t *send, const int
     const size_t sa = ((size_t)st + 255) & ~(size_t)255;
     int rc = stage(c, sa + (size_t)rt + 256);
     if (rc) return rc;
-    hipStream_t s = ctx_stream(c->ctx);
+    hipStream_t s = c->ctx->stream;
     uint8_t *ds = (uint8_t *)c->stage, *dr = (uint8_t *)c->stage + sa;
-    HIPCHK(hipSetDevice(ctx_device(c->ctx)));
+    HIPCHK(hipSetDevice(c->ctx->device));
     if (st) HIPCHK(hipMemcpyAsync(ds, send, (size_t)st, hipMemcpyHostToDevice, s));
     if ((rc = pr_comm_alltoallv_dev(c, ds, send_counts, dr, recv_counts))) return rc;
     if (rt) HIPCHK(hipMemcpyAsync(recv, dr, (size_t)rt, hipMemcpyDeviceToHost, s));
@@ -389,8 +375,8 @@ extern "C" int pr_comm_alltoallv_dev(pr_comm *c, const void *send, const int64_t
     }
     if ((st && !send) || (rt && !recv)) return pr_set_error(PR_ERR_ARG, "null buffer");
     if (c->grp) return local_pull(c, send, send_counts, 0, recv, recv_counts);
-    hipStream_t s = ctx_stream(c->ctx);
-    HIPCHK(hipSetDevice(ctx_device(c->ctx)));
+    hipStream_t s = c->ctx->stream;
+    HIPCHK(hipSetDevice(c->ctx->device));
     const uint8_t *ds = (const uint8_t *)send;
     uint8_t *dr = (uint8_t *)recv;
     std::vector<int64_t> so((size_t)W + 1, 0), ro((size_t)W + 1, 0);
@@ -431,8 +417,8 @@ extern "C" int pr_comm_allgatherv_dev(pr_comm *c, const void *send, const int64_
     }
     if ((counts[me] && !send) || (o[(size_t)W] && !recv)) return pr_set_error(PR_ERR_ARG, "null buffer");
     if (c->grp) return local_pull(c, send, nullptr, counts[me], recv, counts);
-    hipStream_t s = ctx_stream(c->ctx);
-    HIPCHK(hipSetDevice(ctx_device(c->ctx)));
+    hipStream_t s = c->ctx->stream;
+    HIPCHK(hipSetDevice(c->ctx->device));
     uint8_t *dr = (uint8_t *)recv;
     const uint8_t *ds = (const uint8_t *)send;
     if (counts[me] && ds != dr + o[(size_t)me])

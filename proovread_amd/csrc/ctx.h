@@ -1,6 +1,8 @@
-// The library's private context (struct pr_ctx) and what the host files that share it need:
-// the error string, HIPCHK, device buffers and their ids, host <-> device copies.
-// Included by prgpu_api.cpp and seed_api.cpp; sw_api.cpp still goes through the ctx_* accessors.
+// The library's one internal header: the private context (struct pr_ctx) and what the host files
+// that share it need: the error string, HIPCHK, device buffers and their ids, host <-> device
+// copies, and every function one host file calls in another, declared once with the file that
+// defines it (those of the HIP-free files in err.h and bam_codec.h, which those files include
+// too).  Included by every *_api.cpp and comm.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,15 +11,15 @@
 #include <vector>
 
 #include "../../include/prgpu.h"
+#include "bam_codec.h"
+#include "cns_plan.h"
+#include "err.h"
 #include "handoff_plan.h"
 #include "sw_dev.h"
 #include "seed_dev.h"
 
 using namespace prgpu;
 
-// sets pr_last_error's text (printf-style), returns `code` (prgpu_api.cpp)
-int set_error(int code, const char *fmt, ...);
-int pr_set_error(int code, const char *msg);
 #define HIPCHK(x)                                                                        \
     do {                                                                                 \
         hipError_t e_ = (x);                                                             \
@@ -25,7 +27,7 @@ int pr_set_error(int code, const char *msg);
             return set_error(PR_ERR_HIP, "%s failed: %s", #x, hipGetErrorString(e_));    \
     } while (0)
 
-// device memory accounting behind pr_mem_stats (prgpu_api.cpp)
+// device memory accounting behind pr_mem_stats, and the error of a failed hipMalloc (prgpu_api.cpp)
 void prgpu_mem_note(const char *grp, int id, int64_t delta);
 int prgpu_oom(const char *grp, int id, size_t want);
 
@@ -76,16 +78,7 @@ struct DevBuf {
     T *as() const { return reinterpret_cast<T *>(p); }
 };
 
-enum CnsBufId {
-    CB_LR_OFF, CB_REF_SEQ, CB_REF_QUAL, CB_IGN_OFF, CB_IGN, CB_ALN_OFF, CB_POS, CB_SCORE, CB_AFLAGS,
-    CB_SEQ_OFF, CB_LSEQ, CB_CIG_OFF, CB_NCIG, CB_SEQ, CB_CIG,
-    CB_A_ST, CB_A_LEN, CB_A_NC, CB_A_BIN, CB_A_CB, CB_A_CE, CB_A_SB, CB_A_RPOS, CB_A_END,
-    CB_SORTED, CB_LST_SCORE, CB_LST_ALN, CB_KEPT, CB_BIN_OFF, CB_BIN_BASES, CB_WORK,
-    CB_OUT_OFF, CB_CHIM_OFF, CB_STATUS, CB_SEQ_LEN, CB_TRACE_LEN, CB_NCIGAR, CB_NCHIM,
-    CB_O_SEQ, CB_O_QUAL, CB_O_TRACE, CB_O_CIG, CB_O_CHIM, CB_PROF, CB_RETRY, CB_K,
-    CB_GSZS, CB_GSZC, CB_GSO, CB_GCO, CB_GTMP,
-    CB_COUNT
-};
+// (the consensus buffers, CnsBufId: cns_plan.h)
 
 // masking buffers (pr_mask_run inputs / outputs, pr_iter_mask output and run lists)
 enum MaskBufId { MB_OFF, MB_SEQ, MB_QUAL, MB_OUT, MB_RUN_OFF, MB_RUNS, MB_TMP, MB_NRUNS, MB_ERR, MB_STATS, MB_COUNT };
@@ -96,22 +89,83 @@ enum SeedBufId {
     SX_LRSEQ, SX_KEY0, SX_KEY1, SX_VAL0, SX_KC, SX_CNTPTR, SX_TEMP, SI_KSPLIT, SX_VAL1, SX_KCC, SX_KOFFC, SX_KCUR,
     SB_DP, SI_TEXT4, SB_ORDER, SI_BLKFR, SD_COUNT
 };
-// the exact-parity layout's exchange (pr_aln_exchange, owned batches): bounds, sort keys and
-// indices, counts, op prefix, send / receive records and CIGAR ops, grouped hand-off inputs,
-// the task's short reads
 // the resident long-read set: pools, the dense offsets of a commit, the commit's staging pools
 // (LS_RSEQ / LS_RQUAL: pr_lrset_snapshot's raw reads; LS_SRSAMP: pr_srset_sample's task sample)
 enum LrSetBufId {
     LS_SEQ, LS_QUAL, LS_MAP, LS_OFF, LS_TSEQ, LS_TQUAL, LS_TMAP, LS_SRSEQ, LS_GSEQ, LS_GQUAL, LS_GMAP, LS_RSEQ, LS_RQUAL,
     LS_SRSAMP, LS_COUNT
 };
+// the exact-parity layout's exchange (pr_aln_exchange, owned batches): bounds, sort keys and
+// indices, counts, op prefix, send / receive records and CIGAR ops, grouped hand-off inputs,
+// the task's short reads
 enum XchgBufId {
     XB_BOUNDS, XB_KEY0, XB_KEY1, XB_IDX0, XB_IDX1, XB_CNT, XB_OPIN, XB_OPAT, XB_SREC, XB_SCIG, XB_TEMP,
     XB_RREC, XB_RCIG, XB_RCIGAT, XB_GCNT, XB_GCNT64, XB_TASKOFF, XB_ERR, XB_GSR, XB_GSTATUS, XB_GPOS, XB_GSCORE,
     XB_GNCIG, XB_GCIGAT, XB_GSTRAND, XB_GPASS, XB_SR, XB_SROFF, XB_COUNT
 };
 
-enum PipeBufId { PB_TASK_OFF, PB_CNT, PB_ERR, PB_ORDER = 10, PB_BIG_LR, PB_BIG_OFF, PB_KEY0, PB_KEY1, PB_COUNT };
+// the hand-off: the tasks' per-read offsets, counts and error flags, the -b/-l filter's keep flags
+// and scratch (PipeDev: keep, fsorted, fbin, fnc, flen, flst, flsti), the hand-off order, and the
+// HBM sort of the big reads: their list, key offsets, key buffers
+enum PipeBufId {
+    PB_TASK_OFF, PB_CNT, PB_ERR, PB_F_KEEP, PB_F_SORTED, PB_F_BIN, PB_F_NC, PB_F_LEN, PB_F_LST, PB_F_LSTI,
+    PB_ORDER, PB_BIG_LR, PB_BIG_OFF, PB_KEY0, PB_KEY1, PB_COUNT
+};
+static_assert(PB_ORDER == 10, "pr_mem_stats and PRGPU_MEM_TRACE report the index");
+
+// the SW stage's buffers (sw_api.cpp); from SWB_CHAIN on: bwa mode (aln_kernels.hip)
+enum SwBufId {
+    SWB_SR, SWB_SR_OFF, SWB_LR, SWB_LR_OFF, SWB_T_SR, SWB_T_LR, SWB_T_STRAND, SWB_T_QBEG, SWB_T_RBEG, SWB_T_SLEN,
+    SWB_QB, SWB_QE, SWB_RB, SWB_RE, SWB_SCORE, SWB_TRUESC, SWB_W, SWB_PASS, SWB_GSCORE, SWB_POS, SWB_NCIG, SWB_STATUS,
+    SWB_CIG, SWB_Z,
+    SWB_CELLS,     // DP cell and cycle counters, the dequeue counter, the spill counters (sw_api.cpp: CELLS_*)
+    SWB_PERM, SWB_BUCKET, SWB_X, SWB_XTRY, SWB_LIST,
+    SWB_CIGSLOT,   // int64 [n+1] prefix of the per-task CIGAR slots
+    SWB_CIGAT,     // int64 [n] first op of each task's CIGAR
+    SWB_EHG,       // HBM DP rows of the general CIGAR kernel (long queries)
+    SWB_CIGOFF,    // pr_sw_download compaction: prefix of ncigar
+    SWB_CIGOUT,    //                            compacted ops
+    SWB_CHAIN, SWB_SEEDOFF, SWB_SEL, SWB_EXTF, SWB_DEC, SWB_RESUME, SWB_ACNT, SWB_AREG, SWB_AIX, SWB_PSCORE, SWB_NPK,
+    SWB_FDONE, SWB_PREQ, SWB_NOUT, SWB_OLIST, SWB_OFLAG, SWB_ATEMP, SWB_AOFF, SWB_ALIST, SWB_AFLAG, SWB_PPOOL, SWB_GLIST,
+    SWB_GKEY0, SWB_GKEY1, SWB_GCNT, SWB_GLROFF, SWB_GPIPE, SWB_GDOWN, SWB_SCANIN, SWB_TLIST, SWB_CNEXT, SWB_HPREV, SWB_ABOX,
+    SWB_RSNAP, SWB_KEYC,
+    SWB_COUNT
+};
+static_assert(SWB_CELLS == 24 && SWB_CIGOUT == 34 && SWB_CHAIN == 35 && SWB_COUNT == 70,
+              "pr_mem_stats and PRGPU_MEM_TRACE report the index");
+
+// the resident SW batch (sw_api.cpp)
+struct SwResident {
+    bool loaded = false;
+    int64_t n_task = 0, n_sr = 0, n_lr = 0;
+    int qmax = 0;
+    DevBuf buf[SWB_COUNT];
+    // bwa mode (pr_sw_batch.t_chain): the tasks are seeds, the outputs reported alignments
+    bool bwa = false;
+    int64_t read_id0 = 0;
+    int64_t n_aln = 0;          // reported alignments of the last launch
+    int ext_rounds = 0;         // extension rounds of the last launch (mem_chain2aln resumes)
+    int64_t n_ext = 0;          // seeds extended
+    int64_t n_rank0 = 0;        // first seeds of the chains (the first round)
+    bool cnext_ready = false;   // cnext written by the device-seed unpack (seed ranks)
+    int64_t n_big = 0;          // bwa mode: reads of more than ALN_WAVE_SEEDS seeds (the lane kernels')
+    std::vector<int32_t> gcnt_host;   // bwa mode: reported alignments per long read of the last regrouping
+    void *side = nullptr;       // hipStream_t: the early final pass beside the later extension rounds
+    void *side_ev[3] = {nullptr, nullptr, nullptr};   // hipEvent_t
+    int64_t n_patch = 0;        // mem_patch_reg global scores computed
+    // bwa mode's bookkeeping kernels of the last launch (timing events, created on first use):
+    // [0, 1] each round's walk, [2, 3] each late final pass, [4, 5] the early final pass (side
+    // stream), [6, 7] its complement on the main stream
+    void *bt_ev[8] = {};
+    float ms_walk = 0.f, ms_final = 0.f, ms_final_early = 0.f;
+    int64_t cig_slots = 0;      // ops in the slots (= first spill op)
+    int64_t n_overflow = 0;     // tasks of the last launch whose CIGAR went to the spill area
+    float ms_ext = 0.f, ms_glob = 0.f;
+    unsigned long long cells[3] = {0, 0, 0};
+    float ms_glob_ring = 0.f;
+    SwEvPool ext_ev;
+};
+void sw_release(SwResident &r);   // sw_api.cpp
 
 struct pr_ctx {
     int device = 0;
@@ -139,8 +193,6 @@ struct pr_ctx {
     bool pipe = false;
     bool pipe_ref_ascii = false;   // pr_iter_batch.ref_seq given: consensus reference in CB_REF_SEQ
     int pipe_sort_cap = 0;
-    // task_off, cnt, err, then the -b/-l filter: keep, sorted, bin, nc, len, lists (3-9), the
-    // hand-off order (10), and the HBM sort of the big reads: their list, key offsets, key buffers
     DevBuf pb[PB_COUNT];
     handp::Plan ho;              // the hand-off's sort plan (explicit tasks: at upload; bwa mode: at launch)
     bool ho_done = false;        // a hand-off ran on this batch (pr_iter_handoff_stats / _order)
@@ -196,10 +248,43 @@ static int download(T *h, const DevBuf &d, size_t n, hipStream_t s, size_t first
     return 0;
 }
 
-// the two halves of pr_cns_upload that pr_cns_upload_bam shares (prgpu_api.cpp): the long-read part
-// of a batch, and the scratch / output buffers once the alignment columns and bounds are set
+// ---------------------------------------------------------------------------
+// functions one host file calls in another, by the file that defines them
+namespace prgpu {
+struct XchgSend;
+}
+
+// cns_api.cpp: the two halves of pr_cns_upload that pr_cns_upload_bam shares: the long-read part
+// of a batch, and the scratch / output buffers once the alignment columns and bounds are set;
+// the buffers of the given cnsp::Group mask sized for the context's n_lr, n_aln, seq_cap, chim_cap
 int cns_upload_long_reads(pr_ctx *c, const pr_cns_batch *b);
 int cns_alloc_resident(pr_ctx *c);
+int cns_ensure(pr_ctx *c, unsigned groups);
 
-// the seed index built in HBM (seed_api.cpp); lr_dev: lr_seq is a device pointer (pr_lrset_index)
+// iter_api.cpp: the iteration batch's upload; dev_*: device sources in place of the batch's host
+// pools (the resident long-read set and the seeding's copies: pr_iter_upload_lrset)
+int iter_upload(pr_ctx *c, const pr_iter_batch *b, bool gpu_seeds, const uint8_t *dev_sr = nullptr,
+                const uint8_t *dev_lr = nullptr, const uint8_t *dev_ref = nullptr, const uint8_t *dev_qual = nullptr);
+
+// xchg_api.cpp: an owned batch's received records regrouped by long read into the hand-off's
+// inputs (pr_iter_launch)
+int own_group(pr_ctx *c, SwPtrs *sp);
+
+// mask_api.cpp: the masking's capacity flag (syncs)
+int mask_check_err(pr_ctx *c);
+
+// seed_api.cpp: the seed index built in HBM; lr_dev: lr_seq is a device pointer (pr_lrset_index)
 int index_build(pr_ctx *c, const uint8_t *lr_seq, const int64_t *lr_off, int n_lr, bool lr_dev);
+
+// sw_api.cpp: device pointers of the resident SW batch (regroup: bwa mode's alignments grouped by
+// long read), the sender's view of its reported alignments, the SW upload with the device-resident
+// seeds of pr_seed_gpu_map, the -b/-l survivors from grouped into SAM order
+int sw_get_ptrs(pr_ctx *c, SwPtrs *p);
+int sw_get_pipe_ptrs(pr_ctx *c, SwPtrs *p, bool regroup);
+int sw_xchg_send(pr_ctx *c, XchgSend *X);
+int sw_upload_device_seeds(pr_ctx *c, const pr_sw_batch *b, const pr_seed_task *dev_tasks, const int64_t *seed_off_h,
+                           const uint8_t *dev_sr = nullptr, const uint8_t *dev_lr = nullptr);
+int sw_keep_to_sam(pr_ctx *c, const uint8_t *keep_grouped, uint8_t *keep_sam);
+
+// comm.cpp: the context a communicator was made on
+pr_ctx *comm_ctx(pr_comm *c);

@@ -1,4 +1,4 @@
-// Planning of the SW -> consensus hand-off's coordinate sort (the driver in prgpu_api.cpp, the
+// Planning of the SW -> consensus hand-off's coordinate sort (the driver in iter_api.cpp, the
 // kernels in pipe_kernels.hip and pipe_big.hip): which long reads sort in LDS and which take the
 // HBM path, the runs and merge passes of the latter, its scratch and the LDS bytes of both, as
 // plain functions of the per-read alignment counts the host already holds.  No HIP here:

@@ -34,12 +34,11 @@
 #include <sys/mman.h>
 
 #include "../../include/prgpu.h"
+#include "err.h"
 #include "seed_core.h"
 #include "seed_dev.h"
 
 namespace seedc = prgpu::seedc;
-
-int pr_set_error(int code, const char *msg);
 
 namespace {
 

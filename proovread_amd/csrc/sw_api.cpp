@@ -8,65 +8,17 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/prgpu.h"
+#include "ctx.h"
 #include "aln_dev.h"
-#include "sw_dev.h"
 #include "sw_pk.h"
 #include "xchg_dev.h"
 
-using namespace prgpu;
-
-// accessors defined in prgpu_api.cpp
-SwResident &ctx_sw(pr_ctx *c);
-void ctx_sw_batch_changed(pr_ctx *c);
-hipStream_t ctx_stream(pr_ctx *c);
-int ctx_device(pr_ctx *c);
-int ctx_ncu(pr_ctx *c);
-hipEvent_t ctx_event(pr_ctx *c, int i);
-int pr_set_error(int code, const char *msg);
-
-#define HIPCHK(x)                                                                 \
-    do {                                                                          \
-        hipError_t e_ = (x);                                                      \
-        if (e_ != hipSuccess) {                                                   \
-            std::string m_ = std::string(#x) + " failed: " + hipGetErrorString(e_); \
-            return pr_set_error(PR_ERR_HIP, m_.c_str());                          \
-        }                                                                         \
-    } while (0)
-
-enum SwBuf {
-    SB_SR, SB_SR_OFF, SB_LR, SB_LR_OFF, SB_T_SR, SB_T_LR, SB_T_STRAND, SB_T_QBEG, SB_T_RBEG, SB_T_SLEN,
-    SB_QB, SB_QE, SB_RB, SB_RE, SB_SCORE, SB_TRUESC, SB_W, SB_PASS, SB_GSCORE, SB_POS, SB_NCIG, SB_STATUS,
-    SB_CIG, SB_Z
-};
-static const int SB_CELLS = 24;
-// layout of the SB_CELLS buffer (zeroed per launch): [0,24) canonical DP cells, [24,56)
+// layout of the SWB_CELLS buffer (zeroed per launch): [0,24) canonical DP cells, [24,56)
 // packed CIGAR kernel phase cycles, [64,68) the LDS CIGAR kernel's dequeue counter
 static const size_t CELLS_BYTES = 128;
 static const size_t CELLS_WORK_OFF = 64;
-static const int SB_PERM = 25;
-static const int SB_BUCKET = 26;
-static const int SB_X = 27;
-static const int SB_XTRY = 28;
-static const int SB_LIST = 29;
-static const int SB_CIGSLOT = 30;   // int64 [n+1] prefix of the per-task CIGAR slots
-static const int SB_CIGAT = 31;     // int64 [n] first op of each task's CIGAR
-static const int SB_EHG = 32;       // HBM DP rows of the general CIGAR kernel (long queries)
-static const int SB_CIGOFF = 33;    // pr_sw_download compaction: prefix of ncigar
-static const int SB_CIGOUT = 34;    //                            compacted ops
-static const size_t SPILL_OFF = 96;   // in the SB_CELLS buffer: 3 x u64 overflow counters
-// bwa mode (aln_kernels.hip)
-enum AlnBuf {
-    SB_CHAIN = 35, SB_SEEDOFF, SB_SEL, SB_EXTF, SB_DEC, SB_RESUME, SB_ACNT, SB_AREG, SB_AIX, SB_PSCORE, SB_NPK,
-    SB_FDONE, SB_PREQ, SB_NOUT, SB_OLIST, SB_OFLAG, SB_ATEMP, SB_AOFF, SB_ALIST, SB_AFLAG, SB_PPOOL, SB_GLIST,
-    SB_GKEY0, SB_GKEY1, SB_GCNT, SB_GLROFF, SB_GPIPE, SB_GDOWN, SB_SCANIN, SB_TLIST, SB_CNEXT, SB_HPREV, SB_ABOX, SB_RSNAP, SB_KEYC, SB_NBUF
-};
-static_assert(SB_NBUF <= 80, "SwResident buffer table");
+static const size_t SPILL_OFF = 96;   // in the SWB_CELLS buffer: 3 x u64 overflow counters
 
-void prgpu_mem_note(const char *grp, int id, int64_t delta);
-int prgpu_oom(const char *grp, int id, size_t want);
-
-namespace prgpu {
 void sw_release(SwResident &r) {
     for (void *&e : r.ext_ev.ev)
         if (e) (void)hipEventDestroy((hipEvent_t)e), e = nullptr;
@@ -75,42 +27,14 @@ void sw_release(SwResident &r) {
     for (void *&e : r.side_ev)
         if (e) (void)hipEventDestroy((hipEvent_t)e), e = nullptr;
     r.side = nullptr;
-    for (int i = 0; i < 80; ++i) {
-        if (r.buf[i]) (void)hipFree(r.buf[i]), prgpu_mem_note("sw", i, -(int64_t)r.cap[i]);
-        r.buf[i] = nullptr;
-        r.cap[i] = 0;
-    }
+    for (DevBuf &b : r.buf) b.release();
     r.loaded = false;
 }
-}  // namespace prgpu
 
-
-static int ensure(SwResident &r, int id, size_t bytes) {
-    if (r.buf[id] && r.cap[id] >= bytes) return 0;
-    if (r.buf[id]) (void)hipFree(r.buf[id]), prgpu_mem_note("sw", id, -(int64_t)r.cap[id]);
-    r.buf[id] = nullptr;
-    r.cap[id] = 0;
-    const size_t want = bytes + 64;   // slack: kernels read whole dwords at the end of byte pools
-    if (hipMalloc(&r.buf[id], want) != hipSuccess) {
-        r.buf[id] = nullptr;
-        return prgpu_oom("sw", id, want);
-    }
-    r.cap[id] = want;
-    prgpu_mem_note("sw", id, (int64_t)want);
-    return 0;
-}
 // The long-read pool starts SB_LR_FRONT bytes into its buffer: the extension kernels read
 // 16-byte reference windows that may begin up to 15 bytes before a read (reverse strand).
 static constexpr size_t SB_LR_FRONT = 64;
-static uint8_t *lr_pool(SwResident &r) { return (uint8_t *)r.buf[SB_LR] + SB_LR_FRONT; }
-
-template <class T>
-static int up(SwResident &r, int id, const T *h, size_t n, hipStream_t s) {
-    int rc = ensure(r, id, n * sizeof(T));
-    if (rc) return rc;
-    if (n && h) HIPCHK(hipMemcpyAsync(r.buf[id], h, n * sizeof(T), hipMemcpyHostToDevice, s));
-    return 0;
-}
+static uint8_t *lr_pool(SwResident &r) { return r.buf[SWB_LR].as<uint8_t>() + SB_LR_FRONT; }
 
 extern "C" void pr_sw_opts_default(pr_sw_opts *o, int finish) {
     o->bin_size = 0;
@@ -139,10 +63,10 @@ static int sw_upload_impl(pr_ctx *c, const pr_sw_batch *b, const pr_seed_task *d
                           const uint8_t *dev_sr = nullptr, const uint8_t *dev_lr = nullptr) {
     if (!c || !b) return pr_set_error(PR_ERR_ARG, "null arg");
     if (b->n_sr < 0 || b->n_lr < 0 || b->n_task < 0) return pr_set_error(PR_ERR_ARG, "negative sizes");
-    HIPCHK(hipSetDevice(ctx_device(c)));
-    SwResident &r = ctx_sw(c);
-    hipStream_t s = ctx_stream(c);
-    ctx_sw_batch_changed(c);   // an exchange of the previous batch must not be consumed
+    HIPCHK(hipSetDevice(c->device));
+    SwResident &r = c->sw;
+    hipStream_t s = c->stream;
+    c->x_ready = c->x_pass = false;   // an exchange of the previous batch must not be consumed
     int qmax = 1;
     for (int i = 0; i < b->n_sr; ++i) {
         const int64_t l = b->sr_off[i + 1] - b->sr_off[i];
@@ -184,47 +108,47 @@ static int sw_upload_impl(pr_ctx *c, const pr_sw_batch *b, const pr_seed_task *d
     if (bwa)
         for (int i = 0; i < b->n_sr; ++i) r.n_big += seed_off[(size_t)i + 1] - seed_off[(size_t)i] > ALN_WAVE_SEEDS;
     int rc;
-    if ((rc = up(r, SB_SR, dev_sr ? nullptr : b->sr_seq, (size_t)b->sr_off[b->n_sr], s)) ||
-        (rc = up(r, SB_SR_OFF, b->sr_off, (size_t)b->n_sr + 1, s)) ||
-        (rc = ensure(r, SB_LR, (size_t)b->lr_off[b->n_lr] + SB_LR_FRONT)) ||
-        (rc = up(r, SB_LR_OFF, b->lr_off, (size_t)b->n_lr + 1, s)))
+    if ((rc = upload(r.buf[SWB_SR], dev_sr ? nullptr : b->sr_seq, (size_t)b->sr_off[b->n_sr], s)) ||
+        (rc = upload(r.buf[SWB_SR_OFF], b->sr_off, (size_t)b->n_sr + 1, s)) ||
+        (rc = r.buf[SWB_LR].ensure((size_t)b->lr_off[b->n_lr] + SB_LR_FRONT)) ||
+        (rc = upload(r.buf[SWB_LR_OFF], b->lr_off, (size_t)b->n_lr + 1, s)))
         return rc;
     if (!dev_lr && b->lr_off[b->n_lr])
         HIPCHK(hipMemcpyAsync(lr_pool(r), b->lr_seq, (size_t)b->lr_off[b->n_lr], hipMemcpyHostToDevice, s));
     if (dev_sr && b->sr_off[b->n_sr])
-        HIPCHK(hipMemcpyAsync(r.buf[SB_SR], dev_sr, (size_t)b->sr_off[b->n_sr], hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(r.buf[SWB_SR].p, dev_sr, (size_t)b->sr_off[b->n_sr], hipMemcpyDeviceToDevice, s));
     if (dev_lr && b->lr_off[b->n_lr])
         HIPCHK(hipMemcpyAsync(lr_pool(r), dev_lr, (size_t)b->lr_off[b->n_lr], hipMemcpyDeviceToDevice, s));
     if (dev_tasks) {   // unpack the device seed list into the task columns, count the first seeds
-        if ((rc = ensure(r, SB_T_SR, (size_t)nt * 4)) || (rc = ensure(r, SB_T_LR, (size_t)nt * 4)) ||
-            (rc = ensure(r, SB_T_STRAND, (size_t)nt)) || (rc = ensure(r, SB_T_QBEG, (size_t)nt * 4)) ||
-            (rc = ensure(r, SB_T_RBEG, (size_t)nt * 4)) || (rc = ensure(r, SB_T_SLEN, (size_t)nt * 4)) ||
-            (rc = ensure(r, SB_CHAIN, (size_t)nt * 4)) || (rc = ensure(r, SB_ACNT, 64)) ||
-            (rc = ensure(r, SB_CNEXT, ((size_t)nt + 1) * 4)))
+        if ((rc = r.buf[SWB_T_SR].ensure((size_t)nt * 4)) || (rc = r.buf[SWB_T_LR].ensure((size_t)nt * 4)) ||
+            (rc = r.buf[SWB_T_STRAND].ensure((size_t)nt)) || (rc = r.buf[SWB_T_QBEG].ensure((size_t)nt * 4)) ||
+            (rc = r.buf[SWB_T_RBEG].ensure((size_t)nt * 4)) || (rc = r.buf[SWB_T_SLEN].ensure((size_t)nt * 4)) ||
+            (rc = r.buf[SWB_CHAIN].ensure((size_t)nt * 4)) || (rc = r.buf[SWB_ACNT].ensure(64)) ||
+            (rc = r.buf[SWB_CNEXT].ensure(((size_t)nt + 1) * 4)))
             return rc;
-        HIPCHK(hipMemsetAsync(r.buf[SB_ACNT], 0, 64, s));
-        int e = aln_launch_unpack_seeds(dev_tasks, nt, (int32_t *)r.buf[SB_T_SR], (int32_t *)r.buf[SB_T_LR],
-                                        (uint8_t *)r.buf[SB_T_STRAND], (int32_t *)r.buf[SB_T_QBEG],
-                                        (int32_t *)r.buf[SB_T_RBEG], (int32_t *)r.buf[SB_T_SLEN],
-                                        (int32_t *)r.buf[SB_CHAIN], (int32_t *)r.buf[SB_ACNT],
-                                        (int32_t *)r.buf[SB_CNEXT], (void *)s);
+        HIPCHK(hipMemsetAsync(r.buf[SWB_ACNT].p, 0, 64, s));
+        int e = aln_launch_unpack_seeds(dev_tasks, nt, (int32_t *)r.buf[SWB_T_SR].p, (int32_t *)r.buf[SWB_T_LR].p,
+                                        (uint8_t *)r.buf[SWB_T_STRAND].p, (int32_t *)r.buf[SWB_T_QBEG].p,
+                                        (int32_t *)r.buf[SWB_T_RBEG].p, (int32_t *)r.buf[SWB_T_SLEN].p,
+                                        (int32_t *)r.buf[SWB_CHAIN].p, (int32_t *)r.buf[SWB_ACNT].p,
+                                        (int32_t *)r.buf[SWB_CNEXT].p, (void *)s);
         if (e) return pr_set_error(PR_ERR_HIP, hipGetErrorString((hipError_t)e));
         int32_t n0 = 0;
-        HIPCHK(hipMemcpyAsync(&n0, r.buf[SB_ACNT], 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&n0, r.buf[SWB_ACNT].p, 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         r.n_rank0 = n0;
         r.cnext_ready = true;
-    } else if ((rc = up(r, SB_T_SR, b->t_sr, nt, s)) || (rc = up(r, SB_T_LR, b->t_lr, nt, s)) ||
-               (rc = up(r, SB_T_STRAND, b->t_strand, nt, s)) || (rc = up(r, SB_T_QBEG, b->t_qbeg, nt, s)) ||
-               (rc = up(r, SB_T_RBEG, b->t_rbeg, nt, s)) || (rc = up(r, SB_T_SLEN, b->t_slen, nt, s))) {
+    } else if ((rc = upload(r.buf[SWB_T_SR], b->t_sr, nt, s)) || (rc = upload(r.buf[SWB_T_LR], b->t_lr, nt, s)) ||
+               (rc = upload(r.buf[SWB_T_STRAND], b->t_strand, nt, s)) || (rc = upload(r.buf[SWB_T_QBEG], b->t_qbeg, nt, s)) ||
+               (rc = upload(r.buf[SWB_T_RBEG], b->t_rbeg, nt, s)) || (rc = upload(r.buf[SWB_T_SLEN], b->t_slen, nt, s))) {
         return rc;
     }
     const size_t n4 = (size_t)(nt + 1) * 4;
-    for (int id : {SB_QB, SB_QE, SB_RB, SB_RE, SB_SCORE, SB_TRUESC, SB_W, SB_GSCORE, SB_POS, SB_NCIG, SB_STATUS})
-        if ((rc = ensure(r, id, n4))) return rc;
-    if ((rc = ensure(r, SB_PERM, (size_t)(nt + 1) * 4)) || (rc = ensure(r, SB_KEYC, (size_t)(nt + 1) * 4)) || (rc = ensure(r, SB_BUCKET, (SW_NBUCKET + 16 + PK_SCAN + 1) * 4)) ||
-        (rc = ensure(r, SB_X, (size_t)(nt + 1) * 4 * 12)) || (rc = ensure(r, SB_XTRY, (size_t)nt + 1)) ||
-        (rc = ensure(r, SB_LIST, (size_t)(nt + 1 + (int64_t)PK_NB * PK_SEG) * 4)))
+    for (int id : {SWB_QB, SWB_QE, SWB_RB, SWB_RE, SWB_SCORE, SWB_TRUESC, SWB_W, SWB_GSCORE, SWB_POS, SWB_NCIG, SWB_STATUS})
+        if ((rc = r.buf[id].ensure(n4))) return rc;
+    if ((rc = r.buf[SWB_PERM].ensure((size_t)(nt + 1) * 4)) || (rc = r.buf[SWB_KEYC].ensure((size_t)(nt + 1) * 4)) || (rc = r.buf[SWB_BUCKET].ensure((SW_NBUCKET + 16 + PK_SCAN + 1) * 4)) ||
+        (rc = r.buf[SWB_X].ensure((size_t)(nt + 1) * 4 * 12)) || (rc = r.buf[SWB_XTRY].ensure((size_t)nt + 1)) ||
+        (rc = r.buf[SWB_LIST].ensure((size_t)(nt + 1 + (int64_t)PK_NB * PK_SEG) * 4)))
         return rc;
     r.bwa = bwa;
     if (!dev_tasks) r.cnext_ready = false;
@@ -232,23 +156,23 @@ static int sw_upload_impl(pr_ctx *c, const pr_sw_batch *b, const pr_seed_task *d
     r.n_aln = 0;
     if (bwa) {
         const size_t n1 = (size_t)nt + 1, r1 = (size_t)b->n_sr + 1;
-        if ((!dev_tasks && (rc = up(r, SB_CHAIN, b->t_chain, (size_t)nt, s))) ||
-            (rc = up(r, SB_SEEDOFF, seed_off.data(), r1, s)) ||
-            (rc = ensure(r, SB_SEL, n1)) || (rc = ensure(r, SB_EXTF, n1)) || (rc = ensure(r, SB_DEC, n1)) ||
-            (rc = ensure(r, SB_RESUME, r1 * 4)) || (rc = ensure(r, SB_ACNT, 64)) ||
-            (rc = ensure(r, SB_AREG, n1 * sizeof(AlnReg))) || (rc = ensure(r, SB_AIX, n1 * 4)) ||
-            (rc = ensure(r, SB_PSCORE, n1 * 4)) || (rc = ensure(r, SB_NPK, r1 * 4)) || (rc = ensure(r, SB_FDONE, r1)) ||
-            (rc = ensure(r, SB_NOUT, r1 * 4)) || (rc = ensure(r, SB_OLIST, n1 * 4)) || (rc = ensure(r, SB_OFLAG, n1 * 4)) ||
-            (rc = ensure(r, SB_AOFF, r1 * 8)) || (rc = ensure(r, SB_ALIST, n1 * 4)) || (rc = ensure(r, SB_AFLAG, n1 * 4)) ||
-            (rc = ensure(r, SB_PREQ, 1024 * sizeof(AlnPatch))) || (rc = ensure(r, SB_CIGSLOT, n1 * 8)) ||
-            (rc = ensure(r, SB_TLIST, n1 * 4)) || (rc = ensure(r, SB_CNEXT, n1 * 4)) || (rc = ensure(r, SB_HPREV, n1 * 4)) ||
-            (rc = ensure(r, SB_ABOX, n1 * sizeof(AlnBox))) || (rc = ensure(r, SB_RSNAP, r1 * 4)) ||
-            (rc = ensure(r, SB_CIGAT, n1 * 8)) || (rc = ensure(r, SB_PASS, n1)) || (rc = ensure(r, SB_CELLS, CELLS_BYTES)))
+        if ((!dev_tasks && (rc = upload(r.buf[SWB_CHAIN], b->t_chain, (size_t)nt, s))) ||
+            (rc = upload(r.buf[SWB_SEEDOFF], seed_off.data(), r1, s)) ||
+            (rc = r.buf[SWB_SEL].ensure(n1)) || (rc = r.buf[SWB_EXTF].ensure(n1)) || (rc = r.buf[SWB_DEC].ensure(n1)) ||
+            (rc = r.buf[SWB_RESUME].ensure(r1 * 4)) || (rc = r.buf[SWB_ACNT].ensure(64)) ||
+            (rc = r.buf[SWB_AREG].ensure(n1 * sizeof(AlnReg))) || (rc = r.buf[SWB_AIX].ensure(n1 * 4)) ||
+            (rc = r.buf[SWB_PSCORE].ensure(n1 * 4)) || (rc = r.buf[SWB_NPK].ensure(r1 * 4)) || (rc = r.buf[SWB_FDONE].ensure(r1)) ||
+            (rc = r.buf[SWB_NOUT].ensure(r1 * 4)) || (rc = r.buf[SWB_OLIST].ensure(n1 * 4)) || (rc = r.buf[SWB_OFLAG].ensure(n1 * 4)) ||
+            (rc = r.buf[SWB_AOFF].ensure(r1 * 8)) || (rc = r.buf[SWB_ALIST].ensure(n1 * 4)) || (rc = r.buf[SWB_AFLAG].ensure(n1 * 4)) ||
+            (rc = r.buf[SWB_PREQ].ensure(1024 * sizeof(AlnPatch))) || (rc = r.buf[SWB_CIGSLOT].ensure(n1 * 8)) ||
+            (rc = r.buf[SWB_TLIST].ensure(n1 * 4)) || (rc = r.buf[SWB_CNEXT].ensure(n1 * 4)) || (rc = r.buf[SWB_HPREV].ensure(n1 * 4)) ||
+            (rc = r.buf[SWB_ABOX].ensure(n1 * sizeof(AlnBox))) || (rc = r.buf[SWB_RSNAP].ensure(r1 * 4)) ||
+            (rc = r.buf[SWB_CIGAT].ensure(n1 * 8)) || (rc = r.buf[SWB_PASS].ensure(n1)) || (rc = r.buf[SWB_CELLS].ensure(CELLS_BYTES)))
             return rc;
         size_t tb = aln_scan_temp_bytes(nt);
         tb = std::max(tb, aln_scan_temp_bytes(b->n_sr));
         tb = std::max(tb, aln_group_temp_bytes(nt, b->n_lr));
-        if ((rc = ensure(r, SB_ATEMP, tb))) return rc;
+        if ((rc = r.buf[SWB_ATEMP].ensure(tb))) return rc;
         r.cig_slots = 0;
         HIPCHK(hipStreamSynchronize(s));
         r.loaded = true;
@@ -269,9 +193,9 @@ static int sw_upload_impl(pr_ctx *c, const pr_sw_batch *b, const pr_seed_task *d
     }
     const int64_t slots = slot[(size_t)nt];
     const int64_t reserve = slots / 16 > (1 << 20) ? slots / 16 : (1 << 20);
-    if ((rc = ensure(r, SB_PASS, (size_t)nt + 1)) || (rc = ensure(r, SB_CIG, (size_t)(slots + reserve) * 4)) ||
-        (rc = up(r, SB_CIGSLOT, slot.data(), slot.size(), s)) || (rc = ensure(r, SB_CIGAT, (size_t)(nt + 1) * 8)) ||
-        (rc = ensure(r, SB_CELLS, CELLS_BYTES)))
+    if ((rc = r.buf[SWB_PASS].ensure((size_t)nt + 1)) || (rc = r.buf[SWB_CIG].ensure((size_t)(slots + reserve) * 4)) ||
+        (rc = upload(r.buf[SWB_CIGSLOT], slot.data(), slot.size(), s)) || (rc = r.buf[SWB_CIGAT].ensure((size_t)(nt + 1) * 8)) ||
+        (rc = r.buf[SWB_CELLS].ensure(CELLS_BYTES)))
         return rc;
     r.cig_slots = slots;
     HIPCHK(hipStreamSynchronize(s));
@@ -285,7 +209,7 @@ static int sw_upload_impl(pr_ctx *c, const pr_sw_batch *b, const pr_seed_task *d
 
 extern "C" int pr_sw_upload(pr_ctx *c, const pr_sw_batch *b) { return sw_upload_impl(c, b, nullptr, nullptr); }
 
-// the iteration's SW upload with the device-resident seeds of pr_seed_gpu_map (prgpu_api.cpp)
+// the iteration's SW upload with the device-resident seeds of pr_seed_gpu_map (iter_api.cpp, xchg_api.cpp)
 int sw_upload_device_seeds(pr_ctx *c, const pr_sw_batch *b, const pr_seed_task *dev_tasks, const int64_t *seed_off_h,
                            const uint8_t *dev_sr, const uint8_t *dev_lr) {
     return sw_upload_impl(c, b, dev_tasks, seed_off_h, dev_sr, dev_lr);
@@ -299,13 +223,13 @@ static AlnDev aln_dev(SwResident &r, const SwDev &D, const pr_sw_opts *o) {
     A.n_lr = (int32_t)r.n_lr;
     A.read_id0 = r.read_id0;
     A.n_big = r.n_big;
-    A.seed_off = (const int64_t *)r.buf[SB_SEEDOFF];
+    A.seed_off = (const int64_t *)r.buf[SWB_SEEDOFF].p;
     A.t_sr = D.t_sr;
     A.t_lr = D.t_lr;
     A.t_qbeg = D.t_qbeg;
     A.t_rbeg = D.t_rbeg;
     A.t_slen = D.t_slen;
-    A.t_chain = (const int32_t *)r.buf[SB_CHAIN];
+    A.t_chain = (const int32_t *)r.buf[SWB_CHAIN].p;
     A.t_strand = D.t_strand;
     A.sr_off = D.sr_off;
     A.lr_off = D.lr_off;
@@ -314,26 +238,26 @@ static AlnDev aln_dev(SwResident &r, const SwDev &D, const pr_sw_opts *o) {
     A.o_qb = D.o_qb; A.o_qe = D.o_qe; A.o_rb = D.o_rb; A.o_re = D.o_re;
     A.o_score = D.o_score; A.o_truesc = D.o_truesc; A.o_w = D.o_w;
     A.o_pass = D.o_pass;
-    A.sel = (uint8_t *)r.buf[SB_SEL];
-    A.ext = (uint8_t *)r.buf[SB_EXTF];
-    A.dec = (uint8_t *)r.buf[SB_DEC];
-    A.resume = (int32_t *)r.buf[SB_RESUME];
-    A.counter = (int32_t *)r.buf[SB_ACNT];
-    A.tlist = (int32_t *)r.buf[SB_TLIST];
-    A.cnext = (int32_t *)r.buf[SB_CNEXT];
+    A.sel = (uint8_t *)r.buf[SWB_SEL].p;
+    A.ext = (uint8_t *)r.buf[SWB_EXTF].p;
+    A.dec = (uint8_t *)r.buf[SWB_DEC].p;
+    A.resume = (int32_t *)r.buf[SWB_RESUME].p;
+    A.counter = (int32_t *)r.buf[SWB_ACNT].p;
+    A.tlist = (int32_t *)r.buf[SWB_TLIST].p;
+    A.cnext = (int32_t *)r.buf[SWB_CNEXT].p;
     A.cnext_ready = r.cnext_ready ? 1 : 0;
-    A.hprev = getenv("PRGPU_ALN_NO_HPREV") ? nullptr : (int32_t *)r.buf[SB_HPREV];
-    A.box = (AlnBox *)r.buf[SB_ABOX];
-    A.R = (AlnReg *)r.buf[SB_AREG];
-    A.ix = (int32_t *)r.buf[SB_AIX];
-    A.pscore = (int32_t *)r.buf[SB_PSCORE];
-    A.npk = (int32_t *)r.buf[SB_NPK];
-    A.fdone = (uint8_t *)r.buf[SB_FDONE];
-    A.preq = (AlnPatch *)r.buf[SB_PREQ];
-    A.preq_cap = (int32_t)(r.cap[SB_PREQ] / sizeof(AlnPatch));
-    A.nout = (int32_t *)r.buf[SB_NOUT];
-    A.olist = (int32_t *)r.buf[SB_OLIST];
-    A.oflag = (int32_t *)r.buf[SB_OFLAG];
+    A.hprev = getenv("PRGPU_ALN_NO_HPREV") ? nullptr : (int32_t *)r.buf[SWB_HPREV].p;
+    A.box = (AlnBox *)r.buf[SWB_ABOX].p;
+    A.R = (AlnReg *)r.buf[SWB_AREG].p;
+    A.ix = (int32_t *)r.buf[SWB_AIX].p;
+    A.pscore = (int32_t *)r.buf[SWB_PSCORE].p;
+    A.npk = (int32_t *)r.buf[SWB_NPK].p;
+    A.fdone = (uint8_t *)r.buf[SWB_FDONE].p;
+    A.preq = (AlnPatch *)r.buf[SWB_PREQ].p;
+    A.preq_cap = (int32_t)(r.buf[SWB_PREQ].cap / sizeof(AlnPatch));
+    A.nout = (int32_t *)r.buf[SWB_NOUT].p;
+    A.olist = (int32_t *)r.buf[SWB_OLIST].p;
+    A.oflag = (int32_t *)r.buf[SWB_OFLAG].p;
     A.a = o->a; A.b = o->b; A.o_del = o->o_del; A.e_del = o->e_del; A.o_ins = o->o_ins; A.e_ins = o->e_ins;
     A.w = o->w;
     A.max_chain_gap = o->max_chain_gap;
@@ -345,15 +269,15 @@ static AlnDev aln_dev(SwResident &r, const SwDev &D, const pr_sw_opts *o) {
 }
 
 // direction slabs of the band-80 ring kernel when it runs beside the fused packed CIGAR kernel
-// (sw_launch_global's side path): after the packed kernel's slabs in SB_Z; null when SB_Z has no
+// (sw_launch_global's side path): after the packed kernel's slabs in SWB_Z; null when SWB_Z has no
 // room for both (split packed kernel, or PRGPU_RING80_SIDE=0)
 static void *ring_side_z(const SwResident &r, const SwDev &D, int grid_pk, int grid_w) {
     const char *e = getenv("PRGPU_RING80_SIDE");
     if ((e && e[0] == '0') || D.pk_chunk > 0) return nullptr;
     const size_t pk = ((size_t)D.z_pk_slab * sizeof(PkDir) * grid_pk + 255) & ~(size_t)255;
     const size_t ring = (size_t)D.z_ring_slab * 4 * grid_w;
-    if (!r.buf[SB_Z] || r.cap[SB_Z] < pk + ring) return nullptr;
-    return (uint8_t *)r.buf[SB_Z] + pk;
+    if (!r.buf[SWB_Z].p || r.buf[SWB_Z].cap < pk + ring) return nullptr;
+    return (uint8_t *)r.buf[SWB_Z].p + pk;
 }
 
 // the side stream (and its events) of the bwa-mode rounds
@@ -384,7 +308,7 @@ static int pk_prepare(pr_ctx *c, SwResident &r, SwDev &D, const SwOptsDev &O) {
     // 55.9 against 56.2 ms with 16 after the branch-free step), PRGPU_PK_WIN=16 for 16
     D.pk_bt_win = fw && atoi(fw) == 16 ? 16 : 8;
     if (!O.pk) return 0;
-    hipStream_t s = ctx_stream(c);
+    hipStream_t s = c->stream;
     int e = sw_launch_pk_order(D, O, 0, (void *)s);
     if (e) return pr_set_error(PR_ERR_HIP, hipGetErrorString((hipError_t)e));
     const char *sp = getenv("PRGPU_PK_SPLIT");
@@ -402,16 +326,16 @@ static int pk_prepare(pr_ctx *c, SwResident &r, SwDev &D, const SwOptsDev &O) {
     per = per < 64 ? 64 : per;
     const int64_t nch = nseg > 0 ? (nseg + per - 1) / per : 1;
     const int64_t chunk = nseg > 0 ? (nseg + nch - 1) / nch : 1;
-    if ((size_t)chunk * slab > r.cap[SB_Z]) {
-        int rc = ensure(r, SB_Z, (size_t)chunk * slab);
+    if ((size_t)chunk * slab > r.buf[SWB_Z].cap) {
+        int rc = r.buf[SWB_Z].ensure((size_t)chunk * slab);
         if (rc) return rc;
     }
-    D.z = (uint8_t *)r.buf[SB_Z];
+    D.z = (uint8_t *)r.buf[SWB_Z].p;
     D.pk_chunk = (int)chunk;
     D.pk_nseg_bound = nseg;
     const char *bw = getenv("PRGPU_PK_BT_WIN");
     D.pk_bt_win = bw && (atoi(bw) == 16 || atoi(bw) == 4) ? atoi(bw) : 8;
-    D.pk_bt_grid = ctx_ncu(c) * sw_pk_bt_occupancy(D.pk_bt_win);
+    D.pk_bt_grid = c->n_cu * sw_pk_bt_occupancy(D.pk_bt_win);
     return 0;
 }
 
@@ -419,15 +343,15 @@ static int pk_prepare(pr_ctx *c, SwResident &r, SwDev &D, const SwOptsDev &O) {
 // mem_reg2sam) with mem_patch_reg rounds, then the CIGAR pass over the reported alignments
 static int bwa_launch(pr_ctx *c, SwResident &r, SwDev &D, const SwOptsDev &O, const pr_sw_opts *o, int grid_w,
                       int grid_pk, int grid_g, int lds_glob) {
-    hipStream_t s = ctx_stream(c);
+    hipStream_t s = c->stream;
     int rc, e;
-    D.sel = (const uint8_t *)r.buf[SB_SEL];
+    D.sel = (const uint8_t *)r.buf[SWB_SEL].p;
     AlnDev A = aln_dev(r, D, o);
     r.ext_rounds = 0;
     r.n_ext = r.n_rank0;   // rank-0 seeds, extended in the first round
     r.n_patch = 0;
     r.n_aln = 0;
-    HIPCHK(hipEventRecord(ctx_event(c, 2), s));
+    HIPCHK(hipEventRecord(c->ev[2], s));
     if (!r.bt_ev[0])
         for (void *&ev : r.bt_ev) {
             hipEvent_t x;
@@ -462,7 +386,7 @@ static int bwa_launch(pr_ctx *c, SwResident &r, SwDev &D, const SwOptsDev &O, co
         D.tsel_n = n_list;
         HIPCHK(hipMemsetAsync(A.counter, 0, 8, s));
         if (n_list) {
-            e = sw_launch_extend(D, O, ctx_ncu(c) * 16, grid_pk, (void *)s, &r.ext_ev);
+            e = sw_launch_extend(D, O, c->n_cu * 16, grid_pk, (void *)s, &r.ext_ev);
             if (e) return pr_set_error(PR_ERR_HIP, hipGetErrorString((hipError_t)e));
         }
         if (heads_side) {
@@ -486,7 +410,7 @@ static int bwa_launch(pr_ctx *c, SwResident &r, SwDev &D, const SwOptsDev &O, co
             if ((rc = side_stream(r))) return rc;
             // the reads finished now, snapshotted on the main stream: the early pass never reads
             // the live resume array the later rounds' walks write
-            int32_t *snap = (int32_t *)r.buf[SB_RSNAP];
+            int32_t *snap = (int32_t *)r.buf[SWB_RSNAP].p;
             HIPCHK(hipMemcpyAsync(snap, A.resume, (size_t)r.n_sr * 4, hipMemcpyDeviceToDevice, s));
             HIPCHK(hipEventRecord((hipEvent_t)r.side_ev[0], s));
             HIPCHK(hipStreamWaitEvent((hipStream_t)r.side, (hipEvent_t)r.side_ev[0], 0));
@@ -506,7 +430,7 @@ static int bwa_launch(pr_ctx *c, SwResident &r, SwDev &D, const SwOptsDev &O, co
     if (early) {   // the reads the early pass skips, beside it (disjoint reads), then join it
         HIPCHK(hipEventRecord(bt[6], s));
         if (!getenv("PRGPU_BWA_NO_COMPLEMENT") &&
-            (e = aln_launch_final(A, (void *)s, (const int32_t *)r.buf[SB_RSNAP], true)))
+            (e = aln_launch_final(A, (void *)s, (const int32_t *)r.buf[SWB_RSNAP].p, true)))
             return pr_set_error(PR_ERR_HIP, hipGetErrorString((hipError_t)e));
         HIPCHK(hipEventRecord(bt[7], s));
         HIPCHK(hipStreamWaitEvent(s, (hipEvent_t)r.side_ev[1], 0));
@@ -530,51 +454,51 @@ static int bwa_launch(pr_ctx *c, SwResident &r, SwDev &D, const SwOptsDev &O, co
         if (round > r.n_task + 2) return pr_set_error(PR_ERR_HIP, "bwa mode: patch rounds do not converge");
         const int n_req = cnt[1] < A.preq_cap ? cnt[1] : A.preq_cap;
         const int64_t stride = 2 * ((int64_t)r.qmax + 2);
-        if ((rc = ensure(r, SB_PPOOL, (size_t)n_req * (size_t)stride * 4))) return rc;
-        if ((e = aln_launch_patch(A, n_req, (int32_t *)r.buf[SB_PPOOL], stride, (void *)s)))
+        if ((rc = r.buf[SWB_PPOOL].ensure((size_t)n_req * (size_t)stride * 4))) return rc;
+        if ((e = aln_launch_patch(A, n_req, (int32_t *)r.buf[SWB_PPOOL].p, stride, (void *)s)))
             return pr_set_error(PR_ERR_HIP, hipGetErrorString((hipError_t)e));
         r.n_patch += n_req;
         if (cnt[1] > A.preq_cap) {   // requests beyond the list are made again next round
             HIPCHK(hipStreamSynchronize(s));
-            if ((rc = ensure(r, SB_PREQ, (size_t)cnt[1] * sizeof(AlnPatch)))) return rc;
-            A.preq = (AlnPatch *)r.buf[SB_PREQ];
-            A.preq_cap = (int32_t)(r.cap[SB_PREQ] / sizeof(AlnPatch));
+            if ((rc = r.buf[SWB_PREQ].ensure((size_t)cnt[1] * sizeof(AlnPatch)))) return rc;
+            A.preq = (AlnPatch *)r.buf[SWB_PREQ].p;
+            A.preq_cap = (int32_t)(r.buf[SWB_PREQ].cap / sizeof(AlnPatch));
         }
     }
     // CIGAR slots of the reported alignments, the pool, then the CIGAR pass over them
     {
         const int64_t nmax = (r.n_task > r.n_sr ? r.n_task : r.n_sr) + 1;
-        if ((rc = ensure(r, SB_SCANIN, (size_t)nmax * 8))) return rc;
+        if ((rc = r.buf[SWB_SCANIN].ensure((size_t)nmax * 8))) return rc;
     }
     if (getenv("PRGPU_BWA_DEBUG"))
         fprintf(stderr, "[bwa] rounds %d, extended %lld, patches %lld\n", r.ext_rounds, (long long)r.n_ext,
                 (long long)r.n_patch);
-    if ((e = aln_launch_cig_slots(A, (int64_t *)r.buf[SB_CIGSLOT], (int64_t *)r.buf[SB_SCANIN], r.buf[SB_ATEMP],
-                                  r.cap[SB_ATEMP], (void *)s)))
+    if ((e = aln_launch_cig_slots(A, (int64_t *)r.buf[SWB_CIGSLOT].p, (int64_t *)r.buf[SWB_SCANIN].p, r.buf[SWB_ATEMP].p,
+                                  r.buf[SWB_ATEMP].cap, (void *)s)))
         return pr_set_error(PR_ERR_HIP, hipGetErrorString((hipError_t)e));
     int64_t slots = 0;
-    HIPCHK(hipMemcpyAsync(&slots, (int64_t *)r.buf[SB_CIGSLOT] + r.n_task, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&slots, (int64_t *)r.buf[SWB_CIGSLOT].p + r.n_task, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     const int64_t reserve = slots / 16 > (1 << 20) ? slots / 16 : (1 << 20);
-    if ((rc = ensure(r, SB_CIG, (size_t)(slots + reserve) * 4))) return rc;
+    if ((rc = r.buf[SWB_CIG].ensure((size_t)(slots + reserve) * 4))) return rc;
     r.cig_slots = slots;
-    D.o_cig = (uint32_t *)r.buf[SB_CIG];
-    D.cig_slot = (const int64_t *)r.buf[SB_CIGSLOT];
+    D.o_cig = (uint32_t *)r.buf[SWB_CIG].p;
+    D.cig_slot = (const int64_t *)r.buf[SWB_CIGSLOT].p;
     D.spill_base = slots;
-    if (r.n_task) HIPCHK(hipMemcpyAsync(r.buf[SB_CIGAT], r.buf[SB_CIGSLOT], (size_t)r.n_task * 8, hipMemcpyDeviceToDevice, s));
-    if ((e = aln_launch_compact(A, (int64_t *)r.buf[SB_AOFF], (int64_t *)r.buf[SB_SCANIN], (int32_t *)r.buf[SB_ALIST],
-                                (int32_t *)r.buf[SB_AFLAG], r.buf[SB_ATEMP], r.cap[SB_ATEMP], (void *)s)))
+    if (r.n_task) HIPCHK(hipMemcpyAsync(r.buf[SWB_CIGAT].p, r.buf[SWB_CIGSLOT].p, (size_t)r.n_task * 8, hipMemcpyDeviceToDevice, s));
+    if ((e = aln_launch_compact(A, (int64_t *)r.buf[SWB_AOFF].p, (int64_t *)r.buf[SWB_SCANIN].p, (int32_t *)r.buf[SWB_ALIST].p,
+                                (int32_t *)r.buf[SWB_AFLAG].p, r.buf[SWB_ATEMP].p, r.buf[SWB_ATEMP].cap, (void *)s)))
         return pr_set_error(PR_ERR_HIP, hipGetErrorString((hipError_t)e));
-    HIPCHK(hipMemcpyAsync(&r.n_aln, (int64_t *)r.buf[SB_AOFF] + r.n_sr, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&r.n_aln, (int64_t *)r.buf[SWB_AOFF].p + r.n_sr, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    D.tsel = (const int32_t *)r.buf[SB_ALIST];   // the CIGAR pass over the reported alignments
+    D.tsel = (const int32_t *)r.buf[SWB_ALIST].p;   // the CIGAR pass over the reported alignments
     D.tsel_n = r.n_aln;
-    HIPCHK(hipEventRecord(ctx_event(c, 3), s));
+    HIPCHK(hipEventRecord(c->ev[3], s));
     if (r.n_aln) {
         if ((rc = pk_prepare(c, r, D, O))) return rc;
         if ((rc = side_stream(r))) return rc;
-        e = sw_launch_global(D, O, grid_w, grid_pk, grid_g, lds_glob, (void *)s, (void *)ctx_event(c, 6),
-                             (void *)ctx_event(c, 7), true, r.side, r.side_ev[0], r.side_ev[2],
+        e = sw_launch_global(D, O, grid_w, grid_pk, grid_g, lds_glob, (void *)s, (void *)c->ev[6],
+                             (void *)c->ev[7], true, r.side, r.side_ev[0], r.side_ev[2],
                              ring_side_z(r, D, grid_pk, grid_w), r.side_ev[1]);
         if (e) return pr_set_error(PR_ERR_HIP, hipGetErrorString((hipError_t)e));
     }
@@ -583,15 +507,15 @@ static int bwa_launch(pr_ctx *c, SwResident &r, SwDev &D, const SwOptsDev &O, co
     HIPCHK(hipStreamSynchronize(s));
     if (sp[0]) {
         const size_t need = (size_t)(r.cig_slots + (int64_t)sp[1]) * 4;
-        if (need > r.cap[SB_CIG]) {   // grow the pool, keeping the slots
+        if (need > r.buf[SWB_CIG].cap) {   // grow the pool, keeping the slots
             void *np = nullptr;
-            if (hipMalloc(&np, need + need / 8) != hipSuccess) return prgpu_oom("sw CIGAR spill", SB_CIG, need + need / 8);
-            HIPCHK(hipMemcpyAsync(np, r.buf[SB_CIG], (size_t)r.cig_slots * 4, hipMemcpyDeviceToDevice, s));
+            if (hipMalloc(&np, need + need / 8) != hipSuccess) return prgpu_oom("sw CIGAR spill", SWB_CIG, need + need / 8);
+            HIPCHK(hipMemcpyAsync(np, r.buf[SWB_CIG].p, (size_t)r.cig_slots * 4, hipMemcpyDeviceToDevice, s));
             HIPCHK(hipStreamSynchronize(s));
-            (void)hipFree(r.buf[SB_CIG]);
-            prgpu_mem_note("sw", SB_CIG, (int64_t)(need + need / 8) - (int64_t)r.cap[SB_CIG]);
-            r.buf[SB_CIG] = np;
-            r.cap[SB_CIG] = need + need / 8;
+            (void)hipFree(r.buf[SWB_CIG].p);
+            prgpu_mem_note("sw", SWB_CIG, (int64_t)(need + need / 8) - (int64_t)r.buf[SWB_CIG].cap);
+            r.buf[SWB_CIG].p = np;
+            r.buf[SWB_CIG].cap = need + need / 8;
             D.o_cig = (uint32_t *)np;
         }
         HIPCHK(hipMemsetAsync(D.work, 0, 4, s));
@@ -599,13 +523,13 @@ static int bwa_launch(pr_ctx *c, SwResident &r, SwDev &D, const SwOptsDev &O, co
         if (e) return pr_set_error(PR_ERR_HIP, hipGetErrorString((hipError_t)e));
     }
     r.n_overflow = (int64_t)sp[0];
-    HIPCHK(hipEventRecord(ctx_event(c, 0), s));
+    HIPCHK(hipEventRecord(c->ev[0], s));
     return 0;
 }
 
 extern "C" int pr_sw_launch(pr_ctx *c, const pr_sw_opts *o) {
     if (!c || !o) return pr_set_error(PR_ERR_ARG, "null arg");
-    SwResident &r = ctx_sw(c);
+    SwResident &r = c->sw;
     if (!r.loaded) return pr_set_error(PR_ERR_ARG, "no resident SW batch (pr_sw_upload first)");
     if (o->a <= 0 || o->b < 0 || o->e_del <= 0 || o->e_ins <= 0 || o->w <= 0)
         return pr_set_error(PR_ERR_ARG, "bad scoring options");
@@ -613,9 +537,9 @@ extern "C" int pr_sw_launch(pr_ctx *c, const pr_sw_opts *o) {
         return pr_set_error(PR_ERR_ARG, "a * max read length must stay below 8192 (13-bit DP words)");
     if (o->w > 1000) return pr_set_error(PR_ERR_UNSUPPORTED, "band width w > 1000");
     if (o->a > 15 || o->b > 16) return pr_set_error(PR_ERR_UNSUPPORTED, "match score > 15 or mismatch penalty > 16");
-    HIPCHK(hipSetDevice(ctx_device(c)));
+    HIPCHK(hipSetDevice(c->device));
     (void)hipGetLastError();   // a failed earlier call must not poison this one
-    hipStream_t s = ctx_stream(c);
+    hipStream_t s = c->stream;
     SwOptsDev O;
     O.a = o->a; O.b = o->b; O.o_del = o->o_del; O.e_del = o->e_del; O.o_ins = o->o_ins; O.e_ins = o->e_ins;
     O.w = o->w; O.pen_clip5 = o->pen_clip5; O.pen_clip3 = o->pen_clip3; O.zdrop = o->zdrop;
@@ -630,41 +554,41 @@ extern "C" int pr_sw_launch(pr_ctx *c, const pr_sw_opts *o) {
     // reference rows of a region: query + 2 x 2w of extension; a patched (merged) region of bwa
     // mode adds up to 4w more (mem_patch_reg's band bound)
     D.tmax = r.qmax + (r.bwa ? 8 : 4) * o->w + 8;
-    D.sr = (const uint8_t *)r.buf[SB_SR];
-    D.sr_off = (const int64_t *)r.buf[SB_SR_OFF];
+    D.sr = (const uint8_t *)r.buf[SWB_SR].p;
+    D.sr_off = (const int64_t *)r.buf[SWB_SR_OFF].p;
     D.lr = lr_pool(r);
-    D.lr_off = (const int64_t *)r.buf[SB_LR_OFF];
-    D.t_sr = (const int32_t *)r.buf[SB_T_SR];
-    D.t_lr = (const int32_t *)r.buf[SB_T_LR];
-    D.t_strand = (const uint8_t *)r.buf[SB_T_STRAND];
-    D.t_qbeg = (const int32_t *)r.buf[SB_T_QBEG];
-    D.t_rbeg = (const int32_t *)r.buf[SB_T_RBEG];
-    D.t_slen = (const int32_t *)r.buf[SB_T_SLEN];
-    D.o_qb = (int32_t *)r.buf[SB_QB];
-    D.o_qe = (int32_t *)r.buf[SB_QE];
-    D.o_rb = (int32_t *)r.buf[SB_RB];
-    D.o_re = (int32_t *)r.buf[SB_RE];
-    D.o_score = (int32_t *)r.buf[SB_SCORE];
-    D.o_truesc = (int32_t *)r.buf[SB_TRUESC];
-    D.o_w = (int32_t *)r.buf[SB_W];
-    D.o_pass = (uint8_t *)r.buf[SB_PASS];
-    D.o_gscore = (int32_t *)r.buf[SB_GSCORE];
-    D.o_pos = (int32_t *)r.buf[SB_POS];
-    D.o_ncig = (int32_t *)r.buf[SB_NCIG];
-    D.o_status = (int32_t *)r.buf[SB_STATUS];
-    D.o_cig = (uint32_t *)r.buf[SB_CIG];
-    D.cig_slot = (const int64_t *)r.buf[SB_CIGSLOT];
-    D.o_cig_at = (int64_t *)r.buf[SB_CIGAT];
-    D.spill = (unsigned long long *)((char *)r.buf[SB_CELLS] + SPILL_OFF);
+    D.lr_off = (const int64_t *)r.buf[SWB_LR_OFF].p;
+    D.t_sr = (const int32_t *)r.buf[SWB_T_SR].p;
+    D.t_lr = (const int32_t *)r.buf[SWB_T_LR].p;
+    D.t_strand = (const uint8_t *)r.buf[SWB_T_STRAND].p;
+    D.t_qbeg = (const int32_t *)r.buf[SWB_T_QBEG].p;
+    D.t_rbeg = (const int32_t *)r.buf[SWB_T_RBEG].p;
+    D.t_slen = (const int32_t *)r.buf[SWB_T_SLEN].p;
+    D.o_qb = (int32_t *)r.buf[SWB_QB].p;
+    D.o_qe = (int32_t *)r.buf[SWB_QE].p;
+    D.o_rb = (int32_t *)r.buf[SWB_RB].p;
+    D.o_re = (int32_t *)r.buf[SWB_RE].p;
+    D.o_score = (int32_t *)r.buf[SWB_SCORE].p;
+    D.o_truesc = (int32_t *)r.buf[SWB_TRUESC].p;
+    D.o_w = (int32_t *)r.buf[SWB_W].p;
+    D.o_pass = (uint8_t *)r.buf[SWB_PASS].p;
+    D.o_gscore = (int32_t *)r.buf[SWB_GSCORE].p;
+    D.o_pos = (int32_t *)r.buf[SWB_POS].p;
+    D.o_ncig = (int32_t *)r.buf[SWB_NCIG].p;
+    D.o_status = (int32_t *)r.buf[SWB_STATUS].p;
+    D.o_cig = (uint32_t *)r.buf[SWB_CIG].p;
+    D.cig_slot = (const int64_t *)r.buf[SWB_CIGSLOT].p;
+    D.o_cig_at = (int64_t *)r.buf[SWB_CIGAT].p;
+    D.spill = (unsigned long long *)((char *)r.buf[SWB_CELLS].p + SPILL_OFF);
     D.spill_base = r.cig_slots;
-    D.cells = (unsigned long long *)r.buf[SB_CELLS];
-    D.work = (int32_t *)((char *)r.buf[SB_CELLS] + CELLS_WORK_OFF);
-    D.perm = (int32_t *)r.buf[SB_PERM];
-    D.keyc = (int32_t *)r.buf[SB_KEYC];
-    D.bucket = (int32_t *)r.buf[SB_BUCKET];
-    D.x = (int32_t *)r.buf[SB_X];
-    D.x_try = (uint8_t *)r.buf[SB_XTRY];
-    D.list = (int32_t *)r.buf[SB_LIST];
+    D.cells = (unsigned long long *)r.buf[SWB_CELLS].p;
+    D.work = (int32_t *)((char *)r.buf[SWB_CELLS].p + CELLS_WORK_OFF);
+    D.perm = (int32_t *)r.buf[SWB_PERM].p;
+    D.keyc = (int32_t *)r.buf[SWB_KEYC].p;
+    D.bucket = (int32_t *)r.buf[SWB_BUCKET].p;
+    D.x = (int32_t *)r.buf[SWB_X].p;
+    D.x_try = (uint8_t *)r.buf[SWB_XTRY].p;
+    D.list = (int32_t *)r.buf[SWB_LIST].p;
     D.list_n = D.bucket + SW_NBUCKET;
     int rc0 = 0;
     D.pk_bucket = D.bucket + SW_NBUCKET + 16;
@@ -679,7 +603,7 @@ extern "C" int pr_sw_launch(pr_ctx *c, const pr_sw_opts *o) {
     const bool eh_hbm_x = (o->w << 1) > 80 && lds_wide + 256 > 160 * 1024;
     const bool eh_hbm = eh_hbm_g || eh_hbm_x;
     const int blocks_per_cu = eh_hbm ? 2 : ((160 * 1024) / (lds_glob + 64) > 0 ? (160 * 1024) / (lds_glob + 64) : 1);
-    int grid_g = ctx_ncu(c) * (blocks_per_cu < 8 ? blocks_per_cu : 8);
+    int grid_g = c->n_cu * (blocks_per_cu < 8 ? blocks_per_cu : 8);
     D.z_slab = (int64_t)D.tmax * ((r.qmax + 3) / 4) * 4 * SW_WAVE;
     {   // direction slabs of the general kernel within 4 GB
         const int64_t gmax = ((int64_t)4 << 30) / (D.z_slab > 0 ? D.z_slab : 1);
@@ -689,12 +613,12 @@ extern "C" int pr_sw_launch(pr_ctx *c, const pr_sw_opts *o) {
         const int row = lds_glob > lds_wide ? lds_glob : lds_wide;
         D.eh_g_stride = (int64_t)((row + 255) & ~255) / 4;
         D.eh_g_blocks = grid_g;
-        if ((rc0 = ensure(r, SB_EHG, (size_t)D.eh_g_stride * 4 * (size_t)grid_g))) return rc0;
-        D.eh_g = (uint32_t *)r.buf[SB_EHG];
+        if ((rc0 = r.buf[SWB_EHG].ensure((size_t)D.eh_g_stride * 4 * (size_t)grid_g))) return rc0;
+        D.eh_g = (uint32_t *)r.buf[SWB_EHG].p;
     }
-    const int grid_w = ctx_ncu(c) * 12;                       // ring kernels: 3 waves per SIMD
+    const int grid_w = c->n_cu * 12;                       // ring kernels: 3 waves per SIMD
     D.z_ring_slab = (int64_t)D.tmax * ((2 * 80 + 2 + 7) / 8) * SW_WAVE;
-    const int grid_pk = ctx_ncu(c) * 8;                       // packed kernel: ~200 VGPRs, 2 waves per SIMD
+    const int grid_pk = c->n_cu * 8;                       // packed kernel: ~200 VGPRs, 2 waves per SIMD
     D.z_pk_slab = (int64_t)PK_TMAX * pk_npair(40) * SW_WAVE;
     size_t zb = (size_t)D.z_slab * grid_g > (size_t)D.z_ring_slab * 4 * grid_w
                     ? (size_t)D.z_slab * grid_g : (size_t)D.z_ring_slab * 4 * grid_w;
@@ -705,9 +629,9 @@ extern "C" int pr_sw_launch(pr_ctx *c, const pr_sw_opts *o) {
         if (both > zb) zb = both;
     }
     int rc;
-    if ((rc = ensure(r, SB_Z, zb))) return rc;
-    D.z = (uint8_t *)r.buf[SB_Z];
-    HIPCHK(hipMemsetAsync(r.buf[SB_CELLS], 0, CELLS_BYTES, s));
+    if ((rc = r.buf[SWB_Z].ensure(zb))) return rc;
+    D.z = (uint8_t *)r.buf[SWB_Z].p;
+    HIPCHK(hipMemsetAsync(r.buf[SWB_CELLS].p, 0, CELLS_BYTES, s));
     for (void *&ev : r.ext_ev.ev)
         if (!ev) {
             hipEvent_t x;
@@ -718,15 +642,15 @@ extern "C" int pr_sw_launch(pr_ctx *c, const pr_sw_opts *o) {
     r.ext_ev.dropped = 0;
     if (r.bwa) return bwa_launch(c, r, D, O, o, grid_w, grid_pk, grid_g, lds_glob);
     if (r.n_task == 0) return 0;
-    HIPCHK(hipMemcpyAsync(r.buf[SB_CIGAT], r.buf[SB_CIGSLOT], (size_t)r.n_task * 8, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipEventRecord(ctx_event(c, 2), s));
-    int e = sw_launch_extend(D, O, ctx_ncu(c) * 16, grid_pk, (void *)s, &r.ext_ev);
+    HIPCHK(hipMemcpyAsync(r.buf[SWB_CIGAT].p, r.buf[SWB_CIGSLOT].p, (size_t)r.n_task * 8, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipEventRecord(c->ev[2], s));
+    int e = sw_launch_extend(D, O, c->n_cu * 16, grid_pk, (void *)s, &r.ext_ev);
     if (e) return pr_set_error(PR_ERR_HIP, hipGetErrorString((hipError_t)e));
 
-    HIPCHK(hipEventRecord(ctx_event(c, 3), s));
+    HIPCHK(hipEventRecord(c->ev[3], s));
     if ((rc = pk_prepare(c, r, D, O))) return rc;
     if ((rc = side_stream(r))) return rc;
-    e = sw_launch_global(D, O, grid_w, grid_pk, grid_g, lds_glob, (void *)s, (void *)ctx_event(c, 6), (void *)ctx_event(c, 7),
+    e = sw_launch_global(D, O, grid_w, grid_pk, grid_g, lds_glob, (void *)s, (void *)c->ev[6], (void *)c->ev[7],
                          true, r.side, r.side_ev[0], r.side_ev[2], ring_side_z(r, D, grid_pk, grid_w), r.side_ev[1]);
     if (e) return pr_set_error(PR_ERR_HIP, hipGetErrorString((hipError_t)e));
     // CIGARs longer than their slots: recompute those tasks into the spill area
@@ -735,15 +659,15 @@ extern "C" int pr_sw_launch(pr_ctx *c, const pr_sw_opts *o) {
     HIPCHK(hipStreamSynchronize(s));
     if (sp[0]) {
         const size_t need = (size_t)(r.cig_slots + (int64_t)sp[1]) * 4;
-        if (need > r.cap[SB_CIG]) {   // grow the pool, keeping the slots
+        if (need > r.buf[SWB_CIG].cap) {   // grow the pool, keeping the slots
             void *np = nullptr;
-            if (hipMalloc(&np, need + need / 8) != hipSuccess) return prgpu_oom("sw CIGAR spill", SB_CIG, need + need / 8);
-            HIPCHK(hipMemcpyAsync(np, r.buf[SB_CIG], (size_t)r.cig_slots * 4, hipMemcpyDeviceToDevice, s));
+            if (hipMalloc(&np, need + need / 8) != hipSuccess) return prgpu_oom("sw CIGAR spill", SWB_CIG, need + need / 8);
+            HIPCHK(hipMemcpyAsync(np, r.buf[SWB_CIG].p, (size_t)r.cig_slots * 4, hipMemcpyDeviceToDevice, s));
             HIPCHK(hipStreamSynchronize(s));
-            (void)hipFree(r.buf[SB_CIG]);
-            prgpu_mem_note("sw", SB_CIG, (int64_t)(need + need / 8) - (int64_t)r.cap[SB_CIG]);
-            r.buf[SB_CIG] = np;
-            r.cap[SB_CIG] = need + need / 8;
+            (void)hipFree(r.buf[SWB_CIG].p);
+            prgpu_mem_note("sw", SWB_CIG, (int64_t)(need + need / 8) - (int64_t)r.buf[SWB_CIG].cap);
+            r.buf[SWB_CIG].p = np;
+            r.buf[SWB_CIG].cap = need + need / 8;
             D.o_cig = (uint32_t *)np;
         }
         HIPCHK(hipMemsetAsync(D.work, 0, 4, s));
@@ -751,17 +675,11 @@ extern "C" int pr_sw_launch(pr_ctx *c, const pr_sw_opts *o) {
         if (e) return pr_set_error(PR_ERR_HIP, hipGetErrorString((hipError_t)e));
     }
     r.n_overflow = (int64_t)sp[0];
-    HIPCHK(hipEventRecord(ctx_event(c, 0), s));
+    HIPCHK(hipEventRecord(c->ev[0], s));
     return 0;
 }
 
-template <class T>
-static int down(T *h, const SwResident &r, int id, size_t n, hipStream_t s) {
-    if (h && n) HIPCHK(hipMemcpyAsync(h, r.buf[id], n * sizeof(T), hipMemcpyDeviceToHost, s));
-    return 0;
-}
-
-// bwa mode: the per-task arrays gathered per reported alignment (SAM order) into SB_GDOWN
+// bwa mode: the per-task arrays gathered per reported alignment (SAM order) into SWB_GDOWN
 struct BwaRows {
     int32_t *qb, *qe, *rb, *re, *score, *truesc, *pos, *ncig, *status, *task;
     int64_t *cig_at;
@@ -770,12 +688,12 @@ struct BwaRows {
     uint8_t *strand;
 };
 static int bwa_gather(pr_ctx *c, SwResident &r, BwaRows &g) {
-    hipStream_t s = ctx_stream(c);
+    hipStream_t s = c->stream;
     const int64_t n = r.n_aln;
     const size_t n1 = (size_t)n + 1;
     int rc;
-    if ((rc = ensure(r, SB_GDOWN, n1 * (12 * 4 + 8 + 2) + 64))) return rc;
-    char *b = (char *)r.buf[SB_GDOWN];
+    if ((rc = r.buf[SWB_GDOWN].ensure(n1 * (12 * 4 + 8 + 2) + 64))) return rc;
+    char *b = (char *)r.buf[SWB_GDOWN].p;
     int32_t **f[12] = {&g.qb, &g.qe, &g.rb, &g.re, &g.score, &g.truesc, &g.pos, &g.ncig, &g.status, &g.task, &g.sr, &g.lr};
     for (int k = 0; k < 12; ++k) *f[k] = (int32_t *)(b + (size_t)k * n1 * 4);
     g.cig_at = (int64_t *)(b + ((12 * n1 * 4 + 7) & ~(size_t)7));
@@ -783,25 +701,25 @@ static int bwa_gather(pr_ctx *c, SwResident &r, BwaRows &g) {
     g.strand = g.pass + n1;
     SwGather G;
     std::memset(&G, 0, sizeof G);
-    G.list = (const int32_t *)r.buf[SB_ALIST];
+    G.list = (const int32_t *)r.buf[SWB_ALIST].p;
     G.n = n;
-    G.t_sr = (const int32_t *)r.buf[SB_T_SR];
-    G.t_lr = (const int32_t *)r.buf[SB_T_LR];
-    G.status = (const int32_t *)r.buf[SB_STATUS];
-    G.pos = (const int32_t *)r.buf[SB_POS];
-    G.score = (const int32_t *)r.buf[SB_SCORE];
-    G.ncig = (const int32_t *)r.buf[SB_NCIG];
-    G.qb = (const int32_t *)r.buf[SB_QB];
-    G.qe = (const int32_t *)r.buf[SB_QE];
-    G.rb = (const int32_t *)r.buf[SB_RB];
-    G.re = (const int32_t *)r.buf[SB_RE];
-    G.truesc = (const int32_t *)r.buf[SB_TRUESC];
-    G.pass = (const uint8_t *)r.buf[SB_PASS];
-    G.cig_at = (const int64_t *)r.buf[SB_CIGAT];
+    G.t_sr = (const int32_t *)r.buf[SWB_T_SR].p;
+    G.t_lr = (const int32_t *)r.buf[SWB_T_LR].p;
+    G.status = (const int32_t *)r.buf[SWB_STATUS].p;
+    G.pos = (const int32_t *)r.buf[SWB_POS].p;
+    G.score = (const int32_t *)r.buf[SWB_SCORE].p;
+    G.ncig = (const int32_t *)r.buf[SWB_NCIG].p;
+    G.qb = (const int32_t *)r.buf[SWB_QB].p;
+    G.qe = (const int32_t *)r.buf[SWB_QE].p;
+    G.rb = (const int32_t *)r.buf[SWB_RB].p;
+    G.re = (const int32_t *)r.buf[SWB_RE].p;
+    G.truesc = (const int32_t *)r.buf[SWB_TRUESC].p;
+    G.pass = (const uint8_t *)r.buf[SWB_PASS].p;
+    G.cig_at = (const int64_t *)r.buf[SWB_CIGAT].p;
     G.o_qb = g.qb; G.o_qe = g.qe; G.o_rb = g.rb; G.o_re = g.re; G.o_score = g.score; G.o_truesc = g.truesc;
     G.o_pos = g.pos; G.o_ncig = g.ncig; G.o_status = g.status; G.o_task = g.task; G.o_cig_at = g.cig_at;
     G.o_pass = g.pass;
-    G.strand = (const uint8_t *)r.buf[SB_T_STRAND];
+    G.strand = (const uint8_t *)r.buf[SWB_T_STRAND].p;
     G.o_sr = g.sr; G.o_lr = g.lr; G.o_strand = g.strand;
     const int e = sw_launch_gather(G, (void *)s);
     if (e) return pr_set_error(PR_ERR_HIP, hipGetErrorString((hipError_t)e));
@@ -809,7 +727,7 @@ static int bwa_gather(pr_ctx *c, SwResident &r, BwaRows &g) {
 }
 
 static int bwa_download(pr_ctx *c, SwResident &r, pr_sw_out *o) {
-    hipStream_t s = ctx_stream(c);
+    hipStream_t s = c->stream;
     BwaRows g;
     int rc;
     if ((rc = bwa_gather(c, r, g))) return rc;
@@ -821,7 +739,7 @@ static int bwa_download(pr_ctx *c, SwResident &r, pr_sw_out *o) {
     if ((rc = d32(o->qb, g.qb)) || (rc = d32(o->qe, g.qe)) || (rc = d32(o->rb, g.rb)) || (rc = d32(o->re, g.re)) ||
         (rc = d32(o->score, g.score)) || (rc = d32(o->truesc, g.truesc)) || (rc = d32(o->pos, g.pos)) ||
         (rc = d32(o->ncigar, g.ncig)) || (rc = d32(o->status, g.status)) || (rc = d32(o->task, g.task)) ||
-        (rc = d32(o->flag, (const int32_t *)r.buf[SB_AFLAG])))
+        (rc = d32(o->flag, (const int32_t *)r.buf[SWB_AFLAG].p)))
         return rc;
     if (o->pass && n) HIPCHK(hipMemcpyAsync(o->pass, g.pass, n, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -837,45 +755,45 @@ static int bwa_download(pr_ctx *c, SwResident &r, pr_sw_out *o) {
     if (!o->cigar) return 0;
     if (off[n] > o->cigar_cap) return pr_set_error(PR_ERR_CAPACITY, "pr_sw_out.cigar_cap below the CIGAR total");
     if (!off[n]) return 0;
-    if ((rc = up(r, SB_CIGOFF, off.data(), n + 1, s)) || (rc = ensure(r, SB_CIGOUT, (size_t)off[n] * 4))) return rc;
-    int e = sw_launch_cig_compact((const uint32_t *)r.buf[SB_CIG], g.cig_at, g.ncig, (const int64_t *)r.buf[SB_CIGOFF],
-                                  (int64_t)n, (uint32_t *)r.buf[SB_CIGOUT], (void *)s);
+    if ((rc = upload(r.buf[SWB_CIGOFF], off.data(), n + 1, s)) || (rc = r.buf[SWB_CIGOUT].ensure((size_t)off[n] * 4))) return rc;
+    int e = sw_launch_cig_compact((const uint32_t *)r.buf[SWB_CIG].p, g.cig_at, g.ncig, (const int64_t *)r.buf[SWB_CIGOFF].p,
+                                  (int64_t)n, (uint32_t *)r.buf[SWB_CIGOUT].p, (void *)s);
     if (e) return pr_set_error(PR_ERR_HIP, hipGetErrorString((hipError_t)e));
-    HIPCHK(hipMemcpyAsync(o->cigar, r.buf[SB_CIGOUT], (size_t)off[n] * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(o->cigar, r.buf[SWB_CIGOUT].p, (size_t)off[n] * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return 0;
 }
 
 extern "C" int pr_sw_download(pr_ctx *c, pr_sw_out *o) {
     if (!c || !o) return pr_set_error(PR_ERR_ARG, "null arg");
-    SwResident &r = ctx_sw(c);
-    HIPCHK(hipSetDevice(ctx_device(c)));
-    hipStream_t s = ctx_stream(c);
+    SwResident &r = c->sw;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
     if (r.n_task) {
         float a = 0.f, b = 0.f;
-        if (hipEventElapsedTime(&a, ctx_event(c, 2), ctx_event(c, 3)) == hipSuccess) r.ms_ext = a;
-        if (hipEventElapsedTime(&b, ctx_event(c, 3), ctx_event(c, 0)) == hipSuccess) r.ms_glob = b;
-        if (hipEventElapsedTime(&b, ctx_event(c, 6), ctx_event(c, 7)) == hipSuccess) r.ms_glob_ring = b;
+        if (hipEventElapsedTime(&a, c->ev[2], c->ev[3]) == hipSuccess) r.ms_ext = a;
+        if (hipEventElapsedTime(&b, c->ev[3], c->ev[0]) == hipSuccess) r.ms_glob = b;
+        if (hipEventElapsedTime(&b, c->ev[6], c->ev[7]) == hipSuccess) r.ms_glob_ring = b;
     }
-    HIPCHK(hipMemcpy(r.cells, r.buf[SB_CELLS], 24, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(r.cells, r.buf[SWB_CELLS].p, 24, hipMemcpyDeviceToHost));
     if (r.bwa) return bwa_download(c, r, o);
     const size_t n = (size_t)r.n_task;
     int rc;
-    if ((rc = down(o->qb, r, SB_QB, n, s)) || (rc = down(o->qe, r, SB_QE, n, s)) ||
-        (rc = down(o->rb, r, SB_RB, n, s)) || (rc = down(o->re, r, SB_RE, n, s)) ||
-        (rc = down(o->score, r, SB_SCORE, n, s)) || (rc = down(o->truesc, r, SB_TRUESC, n, s)) ||
-        (rc = down(o->pos, r, SB_POS, n, s)) || (rc = down(o->ncigar, r, SB_NCIG, n, s)) ||
-        (rc = down(o->pass, r, SB_PASS, n, s)) || (rc = down(o->status, r, SB_STATUS, n, s)))
+    if ((rc = download(o->qb, r.buf[SWB_QB], n, s)) || (rc = download(o->qe, r.buf[SWB_QE], n, s)) ||
+        (rc = download(o->rb, r.buf[SWB_RB], n, s)) || (rc = download(o->re, r.buf[SWB_RE], n, s)) ||
+        (rc = download(o->score, r.buf[SWB_SCORE], n, s)) || (rc = download(o->truesc, r.buf[SWB_TRUESC], n, s)) ||
+        (rc = download(o->pos, r.buf[SWB_POS], n, s)) || (rc = download(o->ncigar, r.buf[SWB_NCIG], n, s)) ||
+        (rc = download(o->pass, r.buf[SWB_PASS], n, s)) || (rc = download(o->status, r.buf[SWB_STATUS], n, s)))
         return rc;
     HIPCHK(hipStreamSynchronize(s));
     if (!o->cigar_off && !o->cigar) return 0;
     // CIGARs: prefix of the op counts (status 0 tasks), then one compaction launch
     std::vector<int32_t> nc(n + 1, 0), st(n + 1, 0);
     if (n) {
-        HIPCHK(hipMemcpy(nc.data(), r.buf[SB_NCIG], n * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(st.data(), r.buf[SB_STATUS], n * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(nc.data(), r.buf[SWB_NCIG].p, n * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(st.data(), r.buf[SWB_STATUS].p, n * 4, hipMemcpyDeviceToHost));
     }
     std::vector<int64_t> off(n + 1, 0);
     for (size_t t = 0; t < n; ++t) off[t + 1] = off[t] + (st[t] == 0 ? nc[t] : 0);
@@ -883,34 +801,34 @@ extern "C" int pr_sw_download(pr_ctx *c, pr_sw_out *o) {
     if (!o->cigar) return 0;
     if (off[n] > o->cigar_cap) return pr_set_error(PR_ERR_CAPACITY, "pr_sw_out.cigar_cap below the CIGAR total");
     if (!off[n]) return 0;
-    if ((rc = up(r, SB_CIGOFF, off.data(), n + 1, s)) || (rc = ensure(r, SB_CIGOUT, (size_t)off[n] * 4))) return rc;
-    int e = sw_launch_cig_compact((const uint32_t *)r.buf[SB_CIG], (const int64_t *)r.buf[SB_CIGAT],
-                                  (const int32_t *)r.buf[SB_NCIG], (const int64_t *)r.buf[SB_CIGOFF], (int64_t)n,
-                                  (uint32_t *)r.buf[SB_CIGOUT], (void *)s);
+    if ((rc = upload(r.buf[SWB_CIGOFF], off.data(), n + 1, s)) || (rc = r.buf[SWB_CIGOUT].ensure((size_t)off[n] * 4))) return rc;
+    int e = sw_launch_cig_compact((const uint32_t *)r.buf[SWB_CIG].p, (const int64_t *)r.buf[SWB_CIGAT].p,
+                                  (const int32_t *)r.buf[SWB_NCIG].p, (const int64_t *)r.buf[SWB_CIGOFF].p, (int64_t)n,
+                                  (uint32_t *)r.buf[SWB_CIGOUT].p, (void *)s);
     if (e) return pr_set_error(PR_ERR_HIP, hipGetErrorString((hipError_t)e));
-    HIPCHK(hipMemcpyAsync(o->cigar, r.buf[SB_CIGOUT], (size_t)off[n] * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(o->cigar, r.buf[SWB_CIGOUT].p, (size_t)off[n] * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return 0;
 }
 
 extern "C" int pr_sw_cigar_total(pr_ctx *c, int64_t *total, int64_t *n_overflow) {
     if (!c || !total) return pr_set_error(PR_ERR_ARG, "null arg");
-    SwResident &r = ctx_sw(c);
+    SwResident &r = c->sw;
     if (!r.loaded) return pr_set_error(PR_ERR_ARG, "no resident SW batch");
-    HIPCHK(hipSetDevice(ctx_device(c)));
-    HIPCHK(hipStreamSynchronize(ctx_stream(c)));
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
     const size_t n = (size_t)(r.bwa ? r.n_aln : r.n_task);
     std::vector<int32_t> nc(n + 1, 0), st(n + 1, 0);
     if (n && r.bwa) {
         BwaRows g;
         int rc = bwa_gather(c, r, g);
         if (rc) return rc;
-        HIPCHK(hipStreamSynchronize(ctx_stream(c)));
+        HIPCHK(hipStreamSynchronize(c->stream));
         HIPCHK(hipMemcpy(nc.data(), g.ncig, n * 4, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(st.data(), g.status, n * 4, hipMemcpyDeviceToHost));
     } else if (n) {
-        HIPCHK(hipMemcpy(nc.data(), r.buf[SB_NCIG], n * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(st.data(), r.buf[SB_STATUS], n * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(nc.data(), r.buf[SWB_NCIG].p, n * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(st.data(), r.buf[SWB_STATUS].p, n * 4, hipMemcpyDeviceToHost));
     }
     int64_t tot = 0;
     for (size_t t = 0; t < n; ++t) tot += st[t] == 0 ? nc[t] : 0;
@@ -921,27 +839,27 @@ extern "C" int pr_sw_cigar_total(pr_ctx *c, int64_t *total, int64_t *n_overflow)
 
 extern "C" int pr_sw_aln_count(pr_ctx *c, int64_t *n_aln) {
     if (!c || !n_aln) return pr_set_error(PR_ERR_ARG, "null arg");
-    SwResident &r = ctx_sw(c);
+    SwResident &r = c->sw;
     if (!r.loaded) return pr_set_error(PR_ERR_ARG, "no resident SW batch");
-    HIPCHK(hipSetDevice(ctx_device(c)));
-    HIPCHK(hipStreamSynchronize(ctx_stream(c)));
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
     *n_aln = r.bwa ? r.n_aln : r.n_task;
     return 0;
 }
 
 // pr_sw_binfilter's keep flags (computed per alignment in the long-read grouping of bwa_group,
-// on the device) into SAM order: the grouping lists the alignments' tasks (SB_GLIST), SAM order
-// lists them too (SB_ALIST), and a task reports at most one alignment
+// on the device) into SAM order: the grouping lists the alignments' tasks (SWB_GLIST), SAM order
+// lists them too (SWB_ALIST), and a task reports at most one alignment
 int sw_keep_to_sam(pr_ctx *c, const uint8_t *keep_grouped, uint8_t *keep_sam) {
-    SwResident &r = ctx_sw(c);
+    SwResident &r = c->sw;
     if (!r.loaded || !r.bwa) return pr_set_error(PR_ERR_ARG, "no resident bwa-mode SW batch");
-    hipStream_t s = ctx_stream(c);
+    hipStream_t s = c->stream;
     const size_t n = (size_t)r.n_aln;
     std::vector<int32_t> gl(n + 1), al(n + 1);
     std::vector<uint8_t> kg(n + 1);
     if (n) {
-        HIPCHK(hipMemcpyAsync(gl.data(), r.buf[SB_GLIST], n * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(al.data(), r.buf[SB_ALIST], n * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(gl.data(), r.buf[SWB_GLIST].p, n * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(al.data(), r.buf[SWB_ALIST].p, n * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(kg.data(), keep_grouped, n, hipMemcpyDeviceToHost, s));
     }
     HIPCHK(hipStreamSynchronize(s));
@@ -960,10 +878,10 @@ extern "C" int pr_sw_sam(pr_ctx *c, const pr_sam_in *in, char **text, int64_t *l
         return pr_set_error(PR_ERR_ARG, "null arg");
     *text = nullptr;
     *len = 0;
-    SwResident &r = ctx_sw(c);
+    SwResident &r = c->sw;
     if (!r.loaded || !r.bwa) return pr_set_error(PR_ERR_ARG, "no resident bwa-mode SW batch (pr_sw_launch first)");
-    HIPCHK(hipSetDevice(ctx_device(c)));
-    hipStream_t s = ctx_stream(c);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
     const size_t n = (size_t)r.n_aln;
@@ -977,7 +895,7 @@ extern "C" int pr_sw_sam(pr_ctx *c, const pr_sam_in *in, char **text, int64_t *l
         return 0;
     };
     if ((rc = d32(pos, g.pos)) || (rc = d32(score, g.score)) || (rc = d32(ncig, g.ncig)) || (rc = d32(st, g.status)) ||
-        (rc = d32(sr, g.sr)) || (rc = d32(lr, g.lr)) || (rc = d32(flag, r.buf[SB_AFLAG])))
+        (rc = d32(sr, g.sr)) || (rc = d32(lr, g.lr)) || (rc = d32(flag, r.buf[SWB_AFLAG].p)))
         return rc;
     if (n) {
         HIPCHK(hipMemcpyAsync(pass.data(), g.pass, n, hipMemcpyDeviceToHost, s));
@@ -995,14 +913,14 @@ extern "C" int pr_sw_sam(pr_ctx *c, const pr_sam_in *in, char **text, int64_t *l
     if (off[n]) {
         std::vector<int32_t> nc_dev(n);
         for (size_t t = 0; t < n; ++t) nc_dev[t] = ncig[t] < 0 ? 0 : ncig[t];
-        if ((rc = up(r, SB_CIGOFF, off.data(), n + 1, s)) || (rc = ensure(r, SB_CIGOUT, (size_t)off[n] * 4))) return rc;
+        if ((rc = upload(r.buf[SWB_CIGOFF], off.data(), n + 1, s)) || (rc = r.buf[SWB_CIGOUT].ensure((size_t)off[n] * 4))) return rc;
         // the compaction reads its op counts from the device: the printed ones, 0 for the rest
         HIPCHK(hipMemcpyAsync(g.ncig, nc_dev.data(), n * 4, hipMemcpyHostToDevice, s));
-        const int e = sw_launch_cig_compact((const uint32_t *)r.buf[SB_CIG], g.cig_at, g.ncig,
-                                            (const int64_t *)r.buf[SB_CIGOFF], (int64_t)n, (uint32_t *)r.buf[SB_CIGOUT],
+        const int e = sw_launch_cig_compact((const uint32_t *)r.buf[SWB_CIG].p, g.cig_at, g.ncig,
+                                            (const int64_t *)r.buf[SWB_CIGOFF].p, (int64_t)n, (uint32_t *)r.buf[SWB_CIGOUT].p,
                                             (void *)s);
         if (e) return pr_set_error(PR_ERR_HIP, hipGetErrorString((hipError_t)e));
-        HIPCHK(hipMemcpyAsync(cig.data(), r.buf[SB_CIGOUT], (size_t)off[n] * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(cig.data(), r.buf[SWB_CIGOUT].p, (size_t)off[n] * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
     }
     const int64_t n_sr = r.n_sr, n_lr = r.n_lr;
@@ -1132,7 +1050,7 @@ extern "C" int pr_sw_sam(pr_ctx *c, const pr_sam_in *in, char **text, int64_t *l
 
 extern "C" int pr_sw_bwa_timing(pr_ctx *c, float *walk_ms, float *final_ms, float *early_final_ms) {
     if (!c) return pr_set_error(PR_ERR_ARG, "null ctx");
-    SwResident &r = ctx_sw(c);
+    SwResident &r = c->sw;
     if (walk_ms) *walk_ms = r.ms_walk;
     if (final_ms) *final_ms = r.ms_final;
     if (early_final_ms) *early_final_ms = r.ms_final_early;
@@ -1141,7 +1059,7 @@ extern "C" int pr_sw_bwa_timing(pr_ctx *c, float *walk_ms, float *final_ms, floa
 
 extern "C" int pr_sw_bwa_stats(pr_ctx *c, int32_t *rounds, int64_t *n_extended, int64_t *n_patch) {
     if (!c) return pr_set_error(PR_ERR_ARG, "null ctx");
-    SwResident &r = ctx_sw(c);
+    SwResident &r = c->sw;
     if (rounds) *rounds = r.ext_rounds;
     if (n_extended) *n_extended = r.n_ext;
     if (n_patch) *n_patch = r.n_patch;
@@ -1157,13 +1075,13 @@ extern "C" int pr_sw_run(pr_ctx *c, const pr_sw_opts *o, const pr_sw_batch *b, p
 
 extern "C" int pr_sw_last_timing(pr_ctx *c, double *ms_extend, double *ms_global) {
     if (!c) return pr_set_error(PR_ERR_ARG, "null ctx");
-    SwResident &r = ctx_sw(c);
+    SwResident &r = c->sw;
     if (r.loaded && r.n_task) {   // from the launch's events (pipelines that never call pr_sw_download)
-        HIPCHK(hipSetDevice(ctx_device(c)));
-        HIPCHK(hipStreamSynchronize(ctx_stream(c)));
+        HIPCHK(hipSetDevice(c->device));
+        HIPCHK(hipStreamSynchronize(c->stream));
         float a = 0.f, b = 0.f;
-        if (hipEventElapsedTime(&a, ctx_event(c, 2), ctx_event(c, 3)) == hipSuccess) r.ms_ext = a;
-        if (hipEventElapsedTime(&b, ctx_event(c, 3), ctx_event(c, 0)) == hipSuccess) r.ms_glob = b;
+        if (hipEventElapsedTime(&a, c->ev[2], c->ev[3]) == hipSuccess) r.ms_ext = a;
+        if (hipEventElapsedTime(&b, c->ev[3], c->ev[0]) == hipSuccess) r.ms_glob = b;
         (void)hipGetLastError();
     }
     if (ms_extend) *ms_extend = r.ms_ext;
@@ -1173,11 +1091,11 @@ extern "C" int pr_sw_last_timing(pr_ctx *c, double *ms_extend, double *ms_global
 
 extern "C" int pr_sw_last_cells(pr_ctx *c, int64_t *ce, int64_t *cg) {
     if (!c) return pr_set_error(PR_ERR_ARG, "null ctx");
-    SwResident &r = ctx_sw(c);
-    if (r.loaded && r.buf[SB_CELLS]) {
-        HIPCHK(hipSetDevice(ctx_device(c)));
-        HIPCHK(hipStreamSynchronize(ctx_stream(c)));
-        HIPCHK(hipMemcpy(r.cells, r.buf[SB_CELLS], 24, hipMemcpyDeviceToHost));
+    SwResident &r = c->sw;
+    if (r.loaded && r.buf[SWB_CELLS].p) {
+        HIPCHK(hipSetDevice(c->device));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipMemcpy(r.cells, r.buf[SWB_CELLS].p, 24, hipMemcpyDeviceToHost));
     }
     if (ce) *ce = (int64_t)r.cells[0];
     if (cg) *cg = (int64_t)r.cells[1];
@@ -1188,13 +1106,13 @@ extern "C" int pr_sw_dominant_kernel(pr_ctx *c, double *ms, int64_t *cells) {
     // the CIGAR pass's register-ring launch (band <= 40): HIP events around that
     // launch alone on the SW stream, and the DP cells it computed
     if (!c) return pr_set_error(PR_ERR_ARG, "null ctx");
-    SwResident &r = ctx_sw(c);
+    SwResident &r = c->sw;
     if (!r.loaded) return pr_set_error(PR_ERR_ARG, "no resident SW batch");
-    HIPCHK(hipSetDevice(ctx_device(c)));
-    HIPCHK(hipStreamSynchronize(ctx_stream(c)));
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
     float b = 0.f;
-    if (r.n_task && hipEventElapsedTime(&b, ctx_event(c, 6), ctx_event(c, 7)) == hipSuccess) r.ms_glob_ring = b;
-    HIPCHK(hipMemcpy(r.cells, r.buf[SB_CELLS], 24, hipMemcpyDeviceToHost));
+    if (r.n_task && hipEventElapsedTime(&b, c->ev[6], c->ev[7]) == hipSuccess) r.ms_glob_ring = b;
+    HIPCHK(hipMemcpy(r.cells, r.buf[SWB_CELLS].p, 24, hipMemcpyDeviceToHost));
     if (ms) *ms = r.ms_glob_ring;
     if (cells) *cells = (int64_t)r.cells[2];
     return 0;
@@ -1205,17 +1123,17 @@ extern "C" int pr_sw_extension_kernels(pr_ctx *c, double *ms, int64_t *cells, in
     // rounds and both band tries): HIP events around each on the SW stream, summed, and the
     // DP cells they computed
     if (!c) return pr_set_error(PR_ERR_ARG, "null ctx");
-    SwResident &r = ctx_sw(c);
+    SwResident &r = c->sw;
     if (!r.loaded) return pr_set_error(PR_ERR_ARG, "no resident SW batch");
-    HIPCHK(hipSetDevice(ctx_device(c)));
-    HIPCHK(hipStreamSynchronize(ctx_stream(c)));
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
     double tot = 0.0;
     for (int i = 0; i + 1 < r.ext_ev.n; i += 2) {
         float a = 0.f;
         HIPCHK(hipEventElapsedTime(&a, (hipEvent_t)r.ext_ev.ev[i], (hipEvent_t)r.ext_ev.ev[i + 1]));
         tot += a;
     }
-    HIPCHK(hipMemcpy(r.cells, r.buf[SB_CELLS], 24, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(r.cells, r.buf[SWB_CELLS].p, 24, hipMemcpyDeviceToHost));
     if (ms) *ms = tot;
     if (cells) *cells = (int64_t)r.cells[0];
     if (launches) *launches = r.ext_ev.n / 2;
@@ -1223,43 +1141,43 @@ extern "C" int pr_sw_extension_kernels(pr_ctx *c, double *ms, int64_t *cells, in
     return 0;
 }
 
-// for the SW -> consensus pipeline (prgpu_api.cpp)
+// for the SW -> consensus pipeline (iter_api.cpp, cns_api.cpp)
 // bwa mode: the reported alignments regrouped by long read (stable) and gathered into the
-// per-task arrays the hand-off reads (SB_GPIPE), with task_off on the device
+// per-task arrays the hand-off reads (SWB_GPIPE), with task_off on the device
 static int bwa_group(pr_ctx *c, SwResident &r, SwPtrs *p) {
-    hipStream_t s = ctx_stream(c);
+    hipStream_t s = c->stream;
     const int64_t n = r.n_aln;
     const size_t n1 = (size_t)n + 1, l1 = (size_t)r.n_lr + 1;
     int rc;
-    if ((rc = ensure(r, SB_GLIST, n1 * 4)) || (rc = ensure(r, SB_GKEY0, n1 * 4)) || (rc = ensure(r, SB_GKEY1, n1 * 4)) ||
-        (rc = ensure(r, SB_GCNT, l1 * 4)) || (rc = ensure(r, SB_GLROFF, l1 * 8)) ||
-        (rc = ensure(r, SB_GPIPE, n1 * (6 * 4 + 8 + 2) + 64)) || (rc = ensure(r, SB_SCANIN, (l1 + n1) * 8)))
+    if ((rc = r.buf[SWB_GLIST].ensure(n1 * 4)) || (rc = r.buf[SWB_GKEY0].ensure(n1 * 4)) || (rc = r.buf[SWB_GKEY1].ensure(n1 * 4)) ||
+        (rc = r.buf[SWB_GCNT].ensure(l1 * 4)) || (rc = r.buf[SWB_GLROFF].ensure(l1 * 8)) ||
+        (rc = r.buf[SWB_GPIPE].ensure(n1 * (6 * 4 + 8 + 2) + 64)) || (rc = r.buf[SWB_SCANIN].ensure((l1 + n1) * 8)))
         return rc;
     size_t tb = aln_group_temp_bytes(n, (int32_t)r.n_lr);
-    if (tb > r.cap[SB_ATEMP] && (rc = ensure(r, SB_ATEMP, tb))) return rc;
-    int e = aln_launch_group_lr((const int32_t *)r.buf[SB_ALIST], (const int32_t *)r.buf[SB_T_LR], n, (int32_t)r.n_lr,
-                                (int32_t *)r.buf[SB_GKEY0], (int32_t *)r.buf[SB_GKEY1], (int32_t *)r.buf[SB_GLIST],
-                                (int32_t *)r.buf[SB_GCNT], (int64_t *)r.buf[SB_GLROFF], (int64_t *)r.buf[SB_SCANIN],
-                                r.buf[SB_ATEMP], r.cap[SB_ATEMP], (void *)s);
+    if (tb > r.buf[SWB_ATEMP].cap && (rc = r.buf[SWB_ATEMP].ensure(tb))) return rc;
+    int e = aln_launch_group_lr((const int32_t *)r.buf[SWB_ALIST].p, (const int32_t *)r.buf[SWB_T_LR].p, n, (int32_t)r.n_lr,
+                                (int32_t *)r.buf[SWB_GKEY0].p, (int32_t *)r.buf[SWB_GKEY1].p, (int32_t *)r.buf[SWB_GLIST].p,
+                                (int32_t *)r.buf[SWB_GCNT].p, (int64_t *)r.buf[SWB_GLROFF].p, (int64_t *)r.buf[SWB_SCANIN].p,
+                                r.buf[SWB_ATEMP].p, r.buf[SWB_ATEMP].cap, (void *)s);
     if (e) return pr_set_error(PR_ERR_HIP, hipGetErrorString((hipError_t)e));
-    char *b = (char *)r.buf[SB_GPIPE];
+    char *b = (char *)r.buf[SWB_GPIPE].p;
     int32_t *o32[6];
     for (int k = 0; k < 6; ++k) o32[k] = (int32_t *)(b + (size_t)k * n1 * 4);
     int64_t *cig_at = (int64_t *)(b + ((6 * n1 * 4 + 7) & ~(size_t)7));
     uint8_t *strand = (uint8_t *)(cig_at + n1), *pass = strand + n1;
     SwGather G;
     std::memset(&G, 0, sizeof G);
-    G.list = (const int32_t *)r.buf[SB_GLIST];
+    G.list = (const int32_t *)r.buf[SWB_GLIST].p;
     G.n = n;
-    G.t_sr = (const int32_t *)r.buf[SB_T_SR];
-    G.t_lr = (const int32_t *)r.buf[SB_T_LR];
-    G.status = (const int32_t *)r.buf[SB_STATUS];
-    G.pos = (const int32_t *)r.buf[SB_POS];
-    G.score = (const int32_t *)r.buf[SB_SCORE];
-    G.ncig = (const int32_t *)r.buf[SB_NCIG];
-    G.strand = (const uint8_t *)r.buf[SB_T_STRAND];
-    G.pass = (const uint8_t *)r.buf[SB_PASS];
-    G.cig_at = (const int64_t *)r.buf[SB_CIGAT];
+    G.t_sr = (const int32_t *)r.buf[SWB_T_SR].p;
+    G.t_lr = (const int32_t *)r.buf[SWB_T_LR].p;
+    G.status = (const int32_t *)r.buf[SWB_STATUS].p;
+    G.pos = (const int32_t *)r.buf[SWB_POS].p;
+    G.score = (const int32_t *)r.buf[SWB_SCORE].p;
+    G.ncig = (const int32_t *)r.buf[SWB_NCIG].p;
+    G.strand = (const uint8_t *)r.buf[SWB_T_STRAND].p;
+    G.pass = (const uint8_t *)r.buf[SWB_PASS].p;
+    G.cig_at = (const int64_t *)r.buf[SWB_CIGAT].p;
     G.o_sr = o32[0]; G.o_lr = o32[1]; G.o_status = o32[2]; G.o_pos = o32[3]; G.o_score = o32[4]; G.o_ncig = o32[5];
     G.o_cig_at = cig_at;
     G.o_strand = strand;
@@ -1267,7 +1185,7 @@ static int bwa_group(pr_ctx *c, SwResident &r, SwPtrs *p) {
     if ((e = sw_launch_gather(G, (void *)s))) return pr_set_error(PR_ERR_HIP, hipGetErrorString((hipError_t)e));
     std::vector<int32_t> &cnt = r.gcnt_host;
     cnt.assign(l1, 0);
-    HIPCHK(hipMemcpyAsync(cnt.data(), r.buf[SB_GCNT], l1 * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(cnt.data(), r.buf[SWB_GCNT].p, l1 * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     int mx = 0;
     for (int64_t i = 0; i < r.n_lr; ++i) mx = cnt[(size_t)i] > mx ? cnt[(size_t)i] : mx;
@@ -1281,7 +1199,7 @@ static int bwa_group(pr_ctx *c, SwResident &r, SwPtrs *p) {
     p->strand = strand;
     p->pass = pass;
     p->n_task = n;
-    p->task_off = (const int64_t *)r.buf[SB_GLROFF];
+    p->task_off = (const int64_t *)r.buf[SWB_GLROFF].p;
     p->max_per_lr = mx;
     p->cnt_host = cnt.data();
     return 0;
@@ -1290,43 +1208,43 @@ static int bwa_group(pr_ctx *c, SwResident &r, SwPtrs *p) {
 // the exchange's view of the last bwa-mode launch: the reported alignments (SAM order) and the
 // per-task arrays they index (xchg_kernels.hip)
 int sw_xchg_send(pr_ctx *c, XchgSend *X) {
-    SwResident &r = ctx_sw(c);
+    SwResident &r = c->sw;
     if (!r.loaded || !r.bwa) return pr_set_error(PR_ERR_ARG, "no resident bwa-mode SW launch (pr_sw_launch first)");
     X->n = r.n_aln;
-    X->alist = (const int32_t *)r.buf[SB_ALIST];
-    X->t_sr = (const int32_t *)r.buf[SB_T_SR];
-    X->t_lr = (const int32_t *)r.buf[SB_T_LR];
-    X->status = (const int32_t *)r.buf[SB_STATUS];
-    X->pos = (const int32_t *)r.buf[SB_POS];
-    X->score = (const int32_t *)r.buf[SB_SCORE];
-    X->ncig = (const int32_t *)r.buf[SB_NCIG];
-    X->strand = (const uint8_t *)r.buf[SB_T_STRAND];
-    X->pass = (const uint8_t *)r.buf[SB_PASS];
-    X->cig_at = (const int64_t *)r.buf[SB_CIGAT];
-    X->cig = (const uint32_t *)r.buf[SB_CIG];
+    X->alist = (const int32_t *)r.buf[SWB_ALIST].p;
+    X->t_sr = (const int32_t *)r.buf[SWB_T_SR].p;
+    X->t_lr = (const int32_t *)r.buf[SWB_T_LR].p;
+    X->status = (const int32_t *)r.buf[SWB_STATUS].p;
+    X->pos = (const int32_t *)r.buf[SWB_POS].p;
+    X->score = (const int32_t *)r.buf[SWB_SCORE].p;
+    X->ncig = (const int32_t *)r.buf[SWB_NCIG].p;
+    X->strand = (const uint8_t *)r.buf[SWB_T_STRAND].p;
+    X->pass = (const uint8_t *)r.buf[SWB_PASS].p;
+    X->cig_at = (const int64_t *)r.buf[SWB_CIGAT].p;
+    X->cig = (const uint32_t *)r.buf[SWB_CIG].p;
     return 0;
 }
 
 int sw_get_ptrs(pr_ctx *c, SwPtrs *p) {
-    SwResident &r = ctx_sw(c);
+    SwResident &r = c->sw;
     if (!r.loaded) return pr_set_error(PR_ERR_ARG, "no resident SW batch");
     p->task_off = nullptr;
     p->max_per_lr = 0;
     p->cnt_host = nullptr;
-    p->sr = (const uint8_t *)r.buf[SB_SR];
+    p->sr = (const uint8_t *)r.buf[SWB_SR].p;
     p->lr = lr_pool(r);
-    p->strand = (const uint8_t *)r.buf[SB_T_STRAND];
-    p->pass = (const uint8_t *)r.buf[SB_PASS];
-    p->sr_off = (const int64_t *)r.buf[SB_SR_OFF];
-    p->lr_off = (const int64_t *)r.buf[SB_LR_OFF];
-    p->t_sr = (const int32_t *)r.buf[SB_T_SR];
-    p->t_lr = (const int32_t *)r.buf[SB_T_LR];
-    p->status = (const int32_t *)r.buf[SB_STATUS];
-    p->pos = (const int32_t *)r.buf[SB_POS];
-    p->score = (const int32_t *)r.buf[SB_SCORE];
-    p->ncig = (const int32_t *)r.buf[SB_NCIG];
-    p->cig = (const uint32_t *)r.buf[SB_CIG];
-    p->cig_at = (const int64_t *)r.buf[SB_CIGAT];
+    p->strand = (const uint8_t *)r.buf[SWB_T_STRAND].p;
+    p->pass = (const uint8_t *)r.buf[SWB_PASS].p;
+    p->sr_off = (const int64_t *)r.buf[SWB_SR_OFF].p;
+    p->lr_off = (const int64_t *)r.buf[SWB_LR_OFF].p;
+    p->t_sr = (const int32_t *)r.buf[SWB_T_SR].p;
+    p->t_lr = (const int32_t *)r.buf[SWB_T_LR].p;
+    p->status = (const int32_t *)r.buf[SWB_STATUS].p;
+    p->pos = (const int32_t *)r.buf[SWB_POS].p;
+    p->score = (const int32_t *)r.buf[SWB_SCORE].p;
+    p->ncig = (const int32_t *)r.buf[SWB_NCIG].p;
+    p->cig = (const uint32_t *)r.buf[SWB_CIG].p;
+    p->cig_at = (const int64_t *)r.buf[SWB_CIGAT].p;
     p->n_task = r.n_task;
     p->n_sr = (int)r.n_sr;
     p->n_lr = (int)r.n_lr;
@@ -1338,12 +1256,12 @@ int sw_get_ptrs(pr_ctx *c, SwPtrs *p) {
 int sw_get_pipe_ptrs(pr_ctx *c, SwPtrs *p, bool regroup) {
     int rc = sw_get_ptrs(c, p);
     if (rc) return rc;
-    SwResident &r = ctx_sw(c);
+    SwResident &r = c->sw;
     if (!r.bwa) return 0;
     if (regroup) return bwa_group(c, r, p);
     const int64_t n = r.n_aln;
     const size_t n1 = (size_t)n + 1;
-    char *b = (char *)r.buf[SB_GPIPE];
+    char *b = (char *)r.buf[SWB_GPIPE].p;
     p->t_sr = (const int32_t *)b;
     p->t_lr = (const int32_t *)(b + n1 * 4);
     p->status = (const int32_t *)(b + 2 * n1 * 4);
@@ -1354,19 +1272,19 @@ int sw_get_pipe_ptrs(pr_ctx *c, SwPtrs *p, bool regroup) {
     p->strand = (const uint8_t *)(p->cig_at + n1);
     p->pass = p->strand + n1;
     p->n_task = n;
-    p->task_off = (const int64_t *)r.buf[SB_GLROFF];
+    p->task_off = (const int64_t *)r.buf[SWB_GLROFF].p;
     return 0;
 }
 
 extern "C" int pr_sw_phase_cycles(pr_ctx *c, int64_t *out4) {
     // wave-cycle totals of the packed CIGAR kernel's phases (masks, DP, backtrack, emit)
     if (!c || !out4) return pr_set_error(PR_ERR_ARG, "null arg");
-    SwResident &r = ctx_sw(c);
+    SwResident &r = c->sw;
     if (!r.loaded) return pr_set_error(PR_ERR_ARG, "no resident SW batch");
-    HIPCHK(hipSetDevice(ctx_device(c)));
-    HIPCHK(hipStreamSynchronize(ctx_stream(c)));
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
     unsigned long long v[10];
-    HIPCHK(hipMemcpy(v, r.buf[SB_CELLS], sizeof v, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(v, r.buf[SWB_CELLS].p, sizeof v, hipMemcpyDeviceToHost));
     for (int q = 0; q < 4; ++q) out4[q] = (int64_t)v[3 + q];
     if (getenv("PRGPU_SW_DEBUG") && (atoi(getenv("PRGPU_SW_DEBUG")) & 4))   // backtrack walk statistics
         fprintf(stderr, "[sw] backtrack: %llu walk steps, %llu off-pair loads\n", v[9], v[7]);

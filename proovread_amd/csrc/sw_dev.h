@@ -100,38 +100,6 @@ struct SwEvPool {
     int dropped = 0;   // marks the full pool could not take (launches left untimed)
 };
 
-struct SwResident {
-    bool loaded = false;
-    int64_t n_task = 0, n_sr = 0, n_lr = 0;
-    int qmax = 0;
-    void *buf[80] = {};
-    size_t cap[80] = {};
-    // bwa mode (pr_sw_batch.t_chain): the tasks are seeds, the outputs reported alignments
-    bool bwa = false;
-    int64_t read_id0 = 0;
-    int64_t n_aln = 0;          // reported alignments of the last launch
-    int ext_rounds = 0;         // extension rounds of the last launch (mem_chain2aln resumes)
-    int64_t n_ext = 0;          // seeds extended
-    int64_t n_rank0 = 0;        // first seeds of the chains (the first round)
-    bool cnext_ready = false;   // cnext written by the device-seed unpack (seed ranks)
-    int64_t n_big = 0;          // bwa mode: reads of more than ALN_WAVE_SEEDS seeds (the lane kernels')
-    std::vector<int32_t> gcnt_host;   // bwa mode: reported alignments per long read of the last regrouping
-    void *side = nullptr;       // hipStream_t: the early final pass beside the later extension rounds
-    void *side_ev[3] = {nullptr, nullptr, nullptr};   // hipEvent_t
-    int64_t n_patch = 0;        // mem_patch_reg global scores computed
-    // bwa mode's bookkeeping kernels of the last launch (timing events, created on first use):
-    // [0, 1] each round's walk, [2, 3] each late final pass, [4, 5] the early final pass (side
-    // stream), [6, 7] its complement on the main stream
-    void *bt_ev[8] = {};
-    float ms_walk = 0.f, ms_final = 0.f, ms_final_early = 0.f;
-    int64_t cig_slots = 0;      // ops in the slots (= first spill op)
-    int64_t n_overflow = 0;     // tasks of the last launch whose CIGAR went to the spill area
-    float ms_ext = 0.f, ms_glob = 0.f;
-    unsigned long long cells[3] = {0, 0, 0};
-    float ms_glob_ring = 0.f;
-    SwEvPool ext_ev;
-};
-
 // device pointers of a resident SW batch (for the SW -> consensus pipeline); in bwa mode
 // the per-task arrays are the reported alignments grouped by long read (task_off)
 struct SwPtrs {
@@ -161,7 +129,6 @@ int sw_launch_lds(const SwDev &D, const SwOptsDev &O, int grid, int lds, void *s
 int sw_launch_overflow(const SwDev &D, const SwOptsDev &O, int grid, int lds, void *stream);
 int sw_launch_cig_compact(const uint32_t *pool, const int64_t *at, const int32_t *ncig, const int64_t *off,
                           int64_t n, uint32_t *out, void *stream);
-void sw_release(SwResident &r);
 // bwa mode: gather the reported alignments by long read (stable: read order inside a long read)
 struct SwGather {
     const int32_t *list;        // alignment -> task

@@ -21,8 +21,7 @@
 #include <vector>
 
 #include "../../include/prgpu.h"
-
-int pr_set_error(int code, const char *msg);
+#include "err.h"
 
 namespace {
 

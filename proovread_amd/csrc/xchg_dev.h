@@ -1,5 +1,5 @@
 // Device side of the exact-parity multi-GPU layout's alignment exchange (xchg_kernels.hip,
-// driven by pr_aln_exchange / pr_iter_launch on an owned batch in prgpu_api.cpp).
+// driven by pr_aln_exchange / pr_iter_launch on an owned batch in xchg_api.cpp).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
