@@ -135,7 +135,8 @@ int pr_comm_init_local(pr_ctx *ctx, pr_comm_group *g, int rank, pr_comm **out);
 /* Sam::Seq class globals (Seq.pm:114-128) + consensus() options.          */
 typedef struct pr_cns_params {
     double max_coverage;      /* --coverage (bam2cns:230); proovread passes min(cov,task)*0.75 */
-    double bin_size;          /* BinSize; bam2cns always uses 20 (bam2cns:186 quirk)     */
+    double bin_size;          /* BinSize; bam2cns always uses 20 (bam2cns:186 quirk);
+                                 with detect_chimera at most 21 (PR_ERR_CAPACITY)        */
     int32_t trim;             /* Sam::Seq->Trim (cfg sr-trim)                            */
     int32_t indel_taboo_length; /* cfg sr-indel-taboo-length (7); 0 => use indel_taboo    */
     double indel_taboo;       /* cfg sr-indel-taboo (0.1)                                */

@@ -646,9 +646,10 @@ int ocns_run(const ocns_params *P, const char *id, const char *ref_seq, const ch
     int nstates = s.states.n;
     const char **rev = (const char **)calloc((size_t)nstates + 1, sizeof(char *));
     for (int i = 0; i < s.states.cap; i++) if (s.states.key[i]) rev[s.states.val[i]] = s.states.key[i];
+    const long ref_len = ref_seq ? (long)strlen(ref_seq) : 0;   /* (once: reads of megabases) */
     for (long c = 0; c < s.S.n; c++) {
         ocol *col = &s.S.c[c];
-        char refc = (ref_seq && c < (long)strlen(ref_seq)) ? ref_seq[c] : 'n';
+        char refc = (ref_seq && c < ref_len) ? ref_seq[c] : 'n';
         if (col->n == 0) {
             os_putc(&seq, ref_seq ? refc : 'n');
             os_putc(&qual, (char)(ocns_freq2phred(0.0) + P->phred_offset));

@@ -181,6 +181,10 @@ extern "C" int pr_cns_launch(pr_ctx *c, const pr_cns_params *p) {
     if (p->qual_weighted)
         return set_error(PR_ERR_UNSUPPORTED, "--qual-weighted (ccseq/utg modes) is not implemented on the GPU path");
     if (!(p->bin_size >= 1.0)) return set_error(PR_ERR_ARG, "bin_size must be >= 1");
+    // a chimera candidate compares up to 6 bins of columns (4 low bins and one on either side)
+    // in LDS tables of CHIM_MAXCOLS columns
+    if (p->detect_chimera && 6.0 * (double)(long)p->bin_size > (double)CHIM_MAXCOLS)
+        return set_error(PR_ERR_CAPACITY, "detect_chimera needs bin_size <= %d (got %g)", CHIM_MAXCOLS / 6, p->bin_size);
     HIPCHK(hipSetDevice(c->device));
     CnsParamsDev P;
     P.max_coverage = p->max_coverage;

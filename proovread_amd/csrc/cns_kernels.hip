@@ -10,7 +10,7 @@
 //   3. insertion-state table   Seq.pm:446-448 first-seen state indices, as an LDS hash
 //                              keyed by the state string with atomicMin first-seen order
 //   4. windowed pileup         Seq.pm:438-461 scatter into per-column state counts
-//                              (LDS atomics, 512-column windows) and
+//                              (LDS atomics, 1024-column windows) and
 //                              Seq.pm:1568-1654 argmax / phred / trace, block scans
 //   5. Trace2cigar             Seq.pm:206-225 run-length encoding
 //   6. chimera                 Seq.pm:774-889 + bam2cns:461-491
@@ -1727,11 +1727,13 @@ __global__ void __launch_bounds__(CNS_THREADS, G::WGCU) cns_lr_kernel(CnsDev D, 
         }
         CNS_TICK(6);
         if (tid == 0) {
-            if (!C->flag) D.status[lr] = 0;
-            D.seq_len[lr] = C->run_seq;
-            D.trace_len[lr] = tlen;
-            D.ncigar[lr] = nruns;
-            D.nchim[lr] = nch;
+            // a read refused in the chimera pass reports no output, like every other refusal
+            const bool ok = !C->flag;
+            if (ok) D.status[lr] = 0;
+            D.seq_len[lr] = ok ? C->run_seq : 0;
+            D.trace_len[lr] = ok ? tlen : 0;
+            D.ncigar[lr] = ok ? nruns : 0;
+            D.nchim[lr] = ok ? nch : 0;
         }
         __syncthreads();
     }

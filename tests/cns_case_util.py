@@ -2,7 +2,9 @@
 from proovread_amd import cns
 
 
-def case_inputs(case):
+def case_inputs(case, bin_size=20.0):
+    """bin_size: Sam::Seq's BinSize, which the case format has no parameter for (a case's
+    coverage may be any float, "1e7" included)."""
     noref = case.p("noref") == "1"
     if noref:
         lr = cns.LongRead(case.ref_id, None, None, "", len(case.ref[1]))
@@ -11,6 +13,7 @@ def case_inputs(case):
     alns = [cns.SamRecord.from_line(l) for l in case.sam]
     params = cns.CnsParams(
         coverage=float(case.p("coverage")),
+        bin_size=float(bin_size),
         max_ins_length=int(case.p("max_ins_length")),
         use_ref_qual=(case.p("use_ref_qual") == "1") and not noref,
         qual_weighted=case.p("qual_weighted") == "1",
@@ -20,4 +23,4 @@ def case_inputs(case):
 
 
 def params_key(p):
-    return (p.coverage, p.max_ins_length, p.use_ref_qual, p.qual_weighted, p.detect_chimera)
+    return (p.coverage, p.bin_size, p.max_ins_length, p.use_ref_qual, p.qual_weighted, p.detect_chimera)

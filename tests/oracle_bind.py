@@ -99,10 +99,11 @@ def mcr_ranges(desc):
     return [(int(a), int(b)) for a, b in re.findall(r"MCR\d+:(\d+),(\d+)", desc)]
 
 
-def run_case(case):
-    """Run the oracle on a casefmt.Case. Returns dict or {'error': rc}."""
+def run_case(case, **over):
+    """Run the oracle on a casefmt.Case. Returns dict or {'error': rc}.  over: OcnsParams fields
+    the case format has no parameter for (bin_size=100.0)."""
     L = lib()
-    P = params_from_case(case)
+    P = params_from_case(case, **over)
     noref = case.p("noref") == "1"
     seq = case.ref[1]
     qual = case.ref[3]

@@ -63,8 +63,8 @@ def test_gpu_matches_reference_batched():
 
 @pytest.mark.parametrize("batched", [False, True])
 def test_gpu_large_geometry_matches_reference(monkeypatch, batched):
-    """The large LDS geometry (state table 4096, 512-column windows: the rerun of reads
-    whose tables outgrow the small one) forced for every read: same bytes as the
+    """The large LDS geometry (state table 2048, 1024-column windows of 8192 (column, state)
+    pairs: the rerun of reads whose tables outgrow the small one) forced for every read: same bytes as the
     reference, one read per launch and all reads of a parameter set in one launch."""
     from proovread_amd import cns
     monkeypatch.setenv("PRGPU_CNS_LARGE", "1")
@@ -117,8 +117,8 @@ def _insertion_heavy_case(name, seed, L, n_aln, every, ins_len, coverage):
 
 @pytest.mark.parametrize("kind", ["states", "pairs"])
 def test_gpu_retry_geometry_matches_oracle(kind):
-    """Reads that overflow the small geometry's tables (> 1024 distinct insertion states, or
-    > 2048 (column, state) pairs in a 1024-column window) are rerun with the large one;
+    """Reads that overflow the small geometry's tables (> 256 distinct insertion states, or
+    > 512 (column, state) pairs in a 1024-column window) are rerun with the large one;
     the result equals the C oracle's."""
     import oracle_bind as ob
     from proovread_amd import cns
