@@ -12,6 +12,11 @@
  * process, minus the SAM text round trip; lib/Prgpu.pm turns the results into the SAM
  * records bwa-proovread prints.
  *
+ * The resident stages (lrset_*, srset_load, seed_map_sampled, iter_upload_lrset, iter_launch,
+ * iter_chim, iter_mask) keep the loop's reads in HBM between tasks, as
+ * proovread_amd/correct.py's GpuStages does; lib/Prgpu/Stages.pm drives them for
+ * bin/prgpu-proovread.
+ *
  * The binding is thin on purpose: it checks that every packed buffer holds what the
  * batch's counts say it must (so the library never reads past a Perl string), calls
  * pr_cns_run, and hands the output pools back as packed strings.  Library errors croak
@@ -225,6 +230,27 @@ static void gpu_seed(pTHX_ pr_ctx *cx, HV *seed_opts, const pr_sw_batch *b) {
         croak("Prgpu: pr_seed_gpu_index_build: %s (%d)", pr_last_error(), rc);
     if ((rc = pr_seed_gpu_map(cx, &so, b->sr_seq, b->sr_off, b->n_sr, NULL, NULL)) != 0)
         croak("Prgpu: pr_seed_gpu_map: %s (%d)", pr_last_error(), rc);
+}
+
+/* a zeroed Perl string of len bytes for the library to fill */
+static SV *new_buf(pTHX_ STRLEN len) {
+    SV *s = newSV(len + 1);
+    SvPOK_on(s);
+    memset(SvPVX(s), 0, len + 1);
+    SvCUR_set(s, len);
+    return s;
+}
+
+/* the hash Prgpu::mask_params returns (hcr-mask scaled to the short-read length) */
+static void fill_mask_params(pTHX_ HV *params, pr_mask_params *p) {
+    pr_mask_params_default(p);
+    p->phred_min = inum(aTHX_ params, "phred_min", p->phred_min);
+    p->phred_max = inum(aTHX_ params, "phred_max", p->phred_max);
+    p->mask_min_len = inum(aTHX_ params, "mask_min_len", p->mask_min_len);
+    p->unmask_min_len = inum(aTHX_ params, "unmask_min_len", p->unmask_min_len);
+    p->mask_reduce = inum(aTHX_ params, "mask_reduce", p->mask_reduce);
+    p->end_ratio = num(aTHX_ params, "end_ratio", p->end_ratio);
+    p->phred_offset = inum(aTHX_ params, "phred_offset", p->phred_offset);
 }
 
 static void pools_batch(pTHX_ HV *batch, pr_sw_batch *b) {
@@ -680,5 +706,424 @@ iter_run(IV ctx, HV *sw_opts, HV *params, HV *batch)
         }
         RETVAL = cns_out_hash(aTHX_ all);
     }
+  OUTPUT:
+    RETVAL
+
+ # ------------------------------------------------------------------ the resident stages
+ #
+ # What GpuStages (proovread_amd/correct.py) calls through iteration.LongReadSet and
+ # iteration.SetIteration at world 1: the long reads, their mapping reference and the whole
+ # short-read input stay in HBM between tasks; a task moves its record ranges in and two
+ # counters (or the finish task's chimera rows) out.  lib/Prgpu/Stages.pm drives them.
+
+void
+lrset_load(IV ctx, SV *off, SV *seq, SV *qual)
+  CODE:
+    /* read-long's output into HBM (pr_lrset_load): ASCII bases and phred+33 qualities in one
+       pool each; the mapping reference starts as the reads */
+    STRLEN lo = 0, ls = 0;
+    const char *o = arg_buf(aTHX_ off, "off", 8, &lo);
+    const char *s = arg_buf(aTHX_ seq, "seq", 0, &ls);
+    const int64_t n = check_off(aTHX_ o, lo, ls, "off");
+    const char *q = arg_buf(aTHX_ qual, "qual", (size_t)i64_at(o, n), NULL);
+    int rc;
+    if (n > INT32_MAX) croak("Prgpu::lrset_load: too many long reads");
+    rc = pr_lrset_load(INT2PTR(pr_ctx *, ctx), (int32_t)n, (const int64_t *)o, (const uint8_t *)s, (const uint8_t *)q);
+    if (rc != 0) croak("Prgpu: pr_lrset_load: %s (%d)", pr_last_error(), rc);
+
+void
+lrset_info(IV ctx)
+  PPCODE:
+    /* -> (long reads, bases) of the resident set */
+    int32_t n = 0;
+    int64_t nb = 0;
+    int rc = pr_lrset_info(INT2PTR(pr_ctx *, ctx), &n, &nb);
+    if (rc != 0) croak("Prgpu: pr_lrset_info: %s (%d)", pr_last_error(), rc);
+    EXTEND(SP, 2);
+    mPUSHi((IV)n);
+    mPUSHi((IV)nb);
+
+void
+lrset_index(IV ctx, int which)
+  CODE:
+    /* the seed index over the mapping reference (0, PR_LRSET_MAP) or the reads (1) */
+    int rc = pr_lrset_index(INT2PTR(pr_ctx *, ctx), which);
+    if (rc != 0) croak("Prgpu: pr_lrset_index: %s (%d)", pr_last_error(), rc);
+
+SV *
+lrset_download(IV ctx, int want_seq, int want_qual, int want_map)
+  CODE:
+    /* -> {off, seq, qual, map}: the set's offsets (packed int64) and the pools asked for */
+    pr_ctx *cx = INT2PTR(pr_ctx *, ctx);
+    static const char *keys[3] = {"seq", "qual", "map"};
+    const int want[3] = {want_seq, want_qual, want_map};
+    SV *s_off, *bufs[3] = {NULL, NULL, NULL};
+    int32_t n = 0;
+    int64_t nb = 0;
+    int rc, k;
+    HV *res;
+    if ((rc = pr_lrset_info(cx, &n, &nb)) != 0) croak("Prgpu: pr_lrset_info: %s (%d)", pr_last_error(), rc);
+    s_off = new_buf(aTHX_ 8 * ((STRLEN)n + 1));
+    for (k = 0; k < 3; ++k)
+        if (want[k]) bufs[k] = new_buf(aTHX_ (STRLEN)nb);
+    rc = pr_lrset_download(cx, (int64_t *)SvPVX(s_off), bufs[0] ? (uint8_t *)SvPVX(bufs[0]) : NULL,
+                           bufs[1] ? (uint8_t *)SvPVX(bufs[1]) : NULL, bufs[2] ? (uint8_t *)SvPVX(bufs[2]) : NULL);
+    if (rc != 0) {
+        SvREFCNT_dec(s_off);
+        for (k = 0; k < 3; ++k)
+            if (bufs[k]) SvREFCNT_dec(bufs[k]);
+        croak("Prgpu: pr_lrset_download: %s (%d)", pr_last_error(), rc);
+    }
+    res = newHV();
+    hv_store(res, "off", 3, s_off, 0);
+    for (k = 0; k < 3; ++k)
+        if (bufs[k]) hv_store(res, keys[k], (I32)strlen(keys[k]), bufs[k], 0);
+    RETVAL = newRV_noinc((SV *)res);
+  OUTPUT:
+    RETVAL
+
+void
+lrset_commit(IV ctx, int flags)
+  CODE:
+    /* the last launch's consensus (flags & 1: and its masked copy as the next mapping
+       reference) replaces the set's reads; world 1, so no communicator */
+    int rc = pr_lrset_commit(INT2PTR(pr_ctx *, ctx), NULL, flags);
+    if (rc != 0) croak("Prgpu: pr_lrset_commit: %s (%d)", pr_last_error(), rc);
+
+void
+srset_load(IV ctx, SV *off, SV *seq)
+  CODE:
+    /* the whole short-read input (nt4, stream order) into HBM once */
+    STRLEN lo = 0, ls = 0;
+    const char *o = arg_buf(aTHX_ off, "off", 8, &lo);
+    const char *s = arg_buf(aTHX_ seq, "seq", 0, &ls);
+    const int64_t n = check_off(aTHX_ o, lo, ls, "off");
+    int rc = pr_srset_load(INT2PTR(pr_ctx *, ctx), n, (const int64_t *)o, (const uint8_t *)s);
+    if (rc != 0) croak("Prgpu: pr_srset_load: %s (%d)", pr_last_error(), rc);
+
+SV *
+seed_map_sampled(IV ctx, HV *opts, SV *ranges)
+  CODE:
+    /* a task's sample -- record ranges [r0, r1) of the resident short reads, packed int64
+       pairs -- gathered and seeded on the device, the seeds kept in HBM -> the reads' status
+       words (packed int32, one per sampled read) */
+    pr_seed_opts o;
+    STRLEN lr = 0;
+    const char *r = arg_buf(aTHX_ ranges, "ranges", 0, &lr);
+    int64_t nr, k, total = 0;
+    SV *st;
+    int rc;
+    if (lr % 16) croak("Prgpu::seed_map_sampled: ranges must hold int64 pairs");
+    nr = (int64_t)(lr / 16);
+    if (nr > INT32_MAX) croak("Prgpu::seed_map_sampled: too many ranges");
+    for (k = 0; k < nr; ++k) {
+        const int64_t r0 = i64_at(r, 2 * k), r1 = i64_at(r, 2 * k + 1);
+        if (r0 < 0 || r1 < r0 || r1 - r0 > INT32_MAX - total) croak("Prgpu::seed_map_sampled: bad record range");
+        total += r1 - r0;
+    }
+    fill_seed_opts(aTHX_ opts, &o);
+    st = new_buf(aTHX_ 4 * (STRLEN)total);
+    rc = pr_seed_gpu_map_sampled(INT2PTR(pr_ctx *, ctx), &o, (const int64_t *)r, (int)nr, (int32_t *)SvPVX(st));
+    if (rc != 0) {
+        SvREFCNT_dec(st);
+        croak("Prgpu: pr_seed_gpu_map_sampled: %s (%d)", pr_last_error(), rc);
+    }
+    RETVAL = st;
+  OUTPUT:
+    RETVAL
+
+IV
+seed_count(IV ctx)
+  CODE:
+    /* seeds of the last device seeding */
+    int64_t n = 0;
+    int rc = pr_seed_gpu_seed_count(INT2PTR(pr_ctx *, ctx), &n);
+    if (rc != 0) croak("Prgpu: pr_seed_gpu_seed_count: %s (%d)", pr_last_error(), rc);
+    RETVAL = (IV)n;
+  OUTPUT:
+    RETVAL
+
+void
+iter_upload_lrset(IV ctx, SV *sr_off)
+  CODE:
+    /* the iteration batch over the resident set: the seeds and the gathered short reads the
+       last seed_map_sampled left in HBM (sr_off: the sample's offsets), the set's reads and
+       qualities as the consensus reference */
+    pr_sw_batch b;
+    STRLEN lo = 0;
+    const char *o = arg_buf(aTHX_ sr_off, "sr_off", 8, &lo);
+    const int64_t n = check_off(aTHX_ o, lo, (STRLEN)-1 >> 1, "sr_off");
+    int rc;
+    if (n > INT32_MAX) croak("Prgpu::iter_upload_lrset: too many short reads");
+    memset(&b, 0, sizeof b);
+    b.n_sr = (int32_t)n;
+    b.sr_off = (const int64_t *)o;
+    rc = pr_iter_upload_lrset(INT2PTR(pr_ctx *, ctx), &b);
+    if (rc != 0) croak("Prgpu: pr_iter_upload_lrset: %s (%d)", pr_last_error(), rc);
+
+void
+iter_launch(IV ctx, HV *sw_opts, HV *params)
+  CODE:
+    /* seed extension, -b/-l filter, hand-off and consensus of the resident batch (async) */
+    pr_sw_opts o;
+    pr_cns_params p;
+    int rc;
+    fill_sw_opts(aTHX_ sw_opts, &o);
+    fill_cns_params(aTHX_ params, &p);
+    rc = pr_iter_launch(INT2PTR(pr_ctx *, ctx), &o, &p);
+    if (rc != 0) croak("Prgpu: pr_iter_launch: %s (%d)", pr_last_error(), rc);
+
+SV *
+iter_chim(IV ctx)
+  CODE:
+    /* the part of the last launch's output the finish task keeps on the host:
+       -> {n_lr, status, nchim, chim_off, chim ([from, to, n_pos, n_cols] int32 rows)} */
+    pr_ctx *cx = INT2PTR(pr_ctx *, ctx);
+    pr_cns_bounds bd;
+    pr_cns_out out;
+    int32_t n = 0;
+    int64_t nt = 0;
+    SV *all[4];
+    static const char *keys[4] = {"status", "nchim", "chim_off", "chim"};
+    unsigned k;
+    int rc;
+    HV *res;
+    if ((rc = pr_iter_bounds(cx, &n, &nt, &bd)) != 0) croak("Prgpu: pr_iter_bounds: %s (%d)", pr_last_error(), rc);
+    all[0] = new_buf(aTHX_ 4 * (STRLEN)n);
+    all[1] = new_buf(aTHX_ 4 * (STRLEN)n);
+    all[2] = new_buf(aTHX_ 8 * ((STRLEN)n + 1));
+    all[3] = new_buf(aTHX_ 16 * (STRLEN)bd.chim_cap);
+    memset(&out, 0, sizeof out);
+    out.status = (int32_t *)SvPVX(all[0]);
+    out.nchim = (int32_t *)SvPVX(all[1]);
+    out.chim_off = (int64_t *)SvPVX(all[2]);
+    out.chim = (int32_t *)SvPVX(all[3]);
+    rc = pr_iter_download(cx, &out);
+    if (rc != 0) {
+        for (k = 0; k < 4; ++k) SvREFCNT_dec(all[k]);
+        croak("Prgpu: pr_iter_download: %s (%d)", pr_last_error(), rc);
+    }
+    res = newHV();
+    for (k = 0; k < 4; ++k) hv_store(res, keys[k], (I32)strlen(keys[k]), all[k], 0);
+    hv_store(res, "n_lr", 4, newSViv((IV)n), 0);
+    RETVAL = newRV_noinc((SV *)res);
+  OUTPUT:
+    RETVAL
+
+IV
+dev_alloc(IV ctx, IV bytes)
+  CODE:
+    /* device memory of the context (the int64[2] statistic iter_mask fills) */
+    void *d = NULL;
+    int rc;
+    if (bytes <= 0) croak("Prgpu::dev_alloc: bytes must be positive");
+    rc = pr_dev_alloc(INT2PTR(pr_ctx *, ctx), (int64_t)bytes, &d);
+    if (rc != 0) croak("Prgpu: pr_dev_alloc: %s (%d)", pr_last_error(), rc);
+    RETVAL = PTR2IV(d);
+  OUTPUT:
+    RETVAL
+
+void
+dev_free(IV ctx, IV dev)
+  CODE:
+    if (ctx && dev) pr_dev_free(INT2PTR(pr_ctx *, ctx), INT2PTR(void *, dev));
+
+SV *
+dev_download(IV ctx, IV dev, IV bytes)
+  CODE:
+    /* bytes of a dev_alloc buffer (the caller's to keep within its size); synchronises */
+    SV *s;
+    int rc;
+    if (!dev || bytes < 0) croak("Prgpu::dev_download: no device buffer");
+    s = new_buf(aTHX_ (STRLEN)bytes);
+    rc = pr_dev_download(INT2PTR(pr_ctx *, ctx), SvPVX(s), INT2PTR(const void *, dev), (int64_t)bytes);
+    if (rc != 0) {
+        SvREFCNT_dec(s);
+        croak("Prgpu: pr_dev_download: %s (%d)", pr_last_error(), rc);
+    }
+    RETVAL = s;
+  OUTPUT:
+    RETVAL
+
+void
+iter_mask(IV ctx, HV *params, IV dev_stats)
+  CODE:
+    /* SeqFilter --phred-mask of the resident consensus (async); {bpt, bpN} go to the device
+       int64[2] dev_stats (dev_alloc(16)) */
+    pr_mask_params p;
+    int rc;
+    if (!dev_stats) croak("Prgpu::iter_mask: no device statistics buffer");
+    fill_mask_params(aTHX_ params, &p);
+    rc = pr_iter_mask(INT2PTR(pr_ctx *, ctx), &p, INT2PTR(int64_t *, dev_stats));
+    if (rc != 0) croak("Prgpu: pr_iter_mask: %s (%d)", pr_last_error(), rc);
+
+void
+stage_ms(IV ctx)
+  PPCODE:
+    /* kernel time (ms, HIP events) of the last index build, seeding and iteration launch:
+       -> (index, seeding, sw_extend, sw_global_cigar, exchange_handoff, consensus) */
+    pr_ctx *cx = INT2PTR(pr_ctx *, ctx);
+    double v[6] = {0, 0, 0, 0, 0, 0};
+    int k;
+    if (pr_seed_gpu_index_last_ms(cx, &v[0]) != 0 || pr_seed_gpu_last_ms(cx, &v[1]) != 0 ||
+        pr_iter_last_timing(cx, &v[2], &v[3], &v[4], &v[5]) != 0)
+        croak("Prgpu: stage_ms: %s", pr_last_error());
+    EXTEND(SP, 6);
+    for (k = 0; k < 6; ++k) mPUSHn(v[k]);
+
+ # ------------------------------------------------------------------ host helpers of the loop
+
+SV *
+fastq4(SV *data)
+  CODE:
+    /* a FASTQ stream of plain 4-line records scanned natively (pr_fastq4_scan, then
+       pr_fastq4_fill sized by it): -> {n, starts, off (packed int64), pool (nt4)}, or undef
+       for anything else (FASTA, multi-line or irregular records: the caller's parser) */
+    STRLEN len = 0;
+    const char *d = arg_buf(aTHX_ data, "data", 0, &len);
+    int64_t n_rec = 0, n_bases = 0;
+    if (len == 0 || pr_fastq4_scan((const uint8_t *)d, (int64_t)len, &n_rec, &n_bases) != 0) {
+        RETVAL = &PL_sv_undef;
+    } else {
+        uint8_t nt4[256];
+        SV *s_st = new_buf(aTHX_ 8 * (STRLEN)n_rec), *s_off = new_buf(aTHX_ 8 * ((STRLEN)n_rec + 1)),
+           *s_pool = new_buf(aTHX_ (STRLEN)n_bases);
+        HV *res;
+        int rc;
+        memset(nt4, 4, sizeof nt4);
+        nt4['A'] = nt4['a'] = 0;
+        nt4['C'] = nt4['c'] = 1;
+        nt4['G'] = nt4['g'] = 2;
+        nt4['T'] = nt4['t'] = 3;
+        rc = pr_fastq4_fill((const uint8_t *)d, (int64_t)len, nt4, (int64_t *)SvPVX(s_st), (int64_t *)SvPVX(s_off),
+                            (uint8_t *)SvPVX(s_pool));
+        if (rc != 0) {
+            SvREFCNT_dec(s_st);
+            SvREFCNT_dec(s_off);
+            SvREFCNT_dec(s_pool);
+            croak("Prgpu: pr_fastq4_fill: %s (%d)", pr_last_error(), rc);
+        }
+        res = newHV();
+        hv_store(res, "n", 1, newSViv((IV)n_rec), 0);
+        hv_store(res, "starts", 6, s_st, 0);
+        hv_store(res, "off", 3, s_off, 0);
+        hv_store(res, "pool", 4, s_pool, 0);
+        RETVAL = newRV_noinc((SV *)res);
+    }
+  OUTPUT:
+    RETVAL
+
+SV *
+trim_params(const char *trim_win)
+  CODE:
+    /* `SeqFilter --trim-win mean,min` (proovread.cfg:152-155) over qual_window's defaults */
+    pr_trim_params p;
+    HV *h;
+    int rc = pr_trim_params_parse(trim_win, &p);
+    if (rc != 0) croak("Prgpu: pr_trim_params_parse: %s (%d)", pr_last_error(), rc);
+    h = newHV();
+    hv_store(h, "size", 4, newSViv(p.size), 0);
+    hv_store(h, "soft", 4, newSViv(p.soft), 0);
+    hv_store(h, "hard", 4, newSViv(p.hard), 0);
+    hv_store(h, "min_len", 7, newSViv(p.min_len), 0);
+    hv_store(h, "phred_offset", 12, newSViv(p.phred_offset), 0);
+    RETVAL = newRV_noinc((SV *)h);
+  OUTPUT:
+    RETVAL
+
+SV *
+trim_windows(HV *params, SV *qual, SV *off, int threads)
+  CODE:
+    /* the windows --trim-win keeps of every quality string (pr_trim_bound + pr_trim_windows):
+       -> {win_off (packed int64, n+1), win ((offset, length) int32 pairs), n_win (int32)} */
+    pr_trim_params p;
+    STRLEN lq = 0, lo = 0;
+    const char *q = arg_buf(aTHX_ qual, "qual", 0, &lq);
+    const char *o = arg_buf(aTHX_ off, "off", 8, &lo);
+    const int64_t n = check_off(aTHX_ o, lo, lq, "off");
+    int64_t cap = 0;
+    int rc;
+    HV *res;
+    if (n > INT32_MAX) croak("Prgpu::trim_windows: too many reads");
+    pr_trim_params_default(&p);
+    p.size = inum(aTHX_ params, "size", p.size);
+    p.soft = inum(aTHX_ params, "soft", p.soft);
+    p.hard = inum(aTHX_ params, "hard", p.hard);
+    p.min_len = inum(aTHX_ params, "min_len", p.min_len);
+    p.phred_offset = inum(aTHX_ params, "phred_offset", p.phred_offset);
+    rc = pr_trim_bound(&p, (int32_t)n, (const int64_t *)o, &cap);
+    if (rc != 0) croak("Prgpu: pr_trim_bound: %s (%d)", pr_last_error(), rc);
+    {
+        SV *s_woff = new_buf(aTHX_ 8 * ((STRLEN)n + 1)), *s_win = new_buf(aTHX_ 8 * (STRLEN)cap),
+           *s_nw = new_buf(aTHX_ 4 * (STRLEN)n);
+        rc = pr_trim_windows(&p, (int32_t)n, (const int64_t *)o, (const uint8_t *)q, (int64_t *)SvPVX(s_woff),
+                             (int32_t *)SvPVX(s_win), (int32_t *)SvPVX(s_nw), threads);
+        if (rc != 0) {
+            SvREFCNT_dec(s_woff);
+            SvREFCNT_dec(s_win);
+            SvREFCNT_dec(s_nw);
+            croak("Prgpu: pr_trim_windows: %s (%d)", pr_last_error(), rc);
+        }
+        res = newHV();
+        hv_store(res, "win_off", 7, s_woff, 0);
+        hv_store(res, "win", 3, s_win, 0);
+        hv_store(res, "n_win", 5, s_nw, 0);
+    }
+    RETVAL = newRV_noinc((SV *)res);
+  OUTPUT:
+    RETVAL
+
+SV *
+seed_opts(HV *opts)
+  CODE:
+    /* every field of the pr_seed_opts an option hash stands for (its defaults filled in) */
+    pr_seed_opts o;
+    HV *h = newHV();
+    fill_seed_opts(aTHX_ opts, &o);
+    hv_store(h, "min_seed_len", 12, newSViv(o.min_seed_len), 0);
+    hv_store(h, "min_chain_weight", 16, newSViv(o.min_chain_weight), 0);
+    hv_store(h, "w", 1, newSViv(o.w), 0);
+    hv_store(h, "split_factor", 12, newSVnv(o.split_factor), 0);
+    hv_store(h, "split_width", 11, newSViv(o.split_width), 0);
+    hv_store(h, "max_mem_intv", 12, newSViv(o.max_mem_intv), 0);
+    hv_store(h, "max_occ", 7, newSViv(o.max_occ), 0);
+    hv_store(h, "drop_ratio", 10, newSVnv(o.drop_ratio), 0);
+    hv_store(h, "max_chain_gap", 13, newSViv(o.max_chain_gap), 0);
+    hv_store(h, "mask_level", 10, newSVnv(o.mask_level), 0);
+    hv_store(h, "a", 1, newSViv(o.a), 0);
+    hv_store(h, "o_del", 5, newSViv(o.o_del), 0);
+    hv_store(h, "e_del", 5, newSViv(o.e_del), 0);
+    hv_store(h, "o_ins", 5, newSViv(o.o_ins), 0);
+    hv_store(h, "e_ins", 5, newSViv(o.e_ins), 0);
+    hv_store(h, "b", 1, newSViv(o.b), 0);
+    RETVAL = newRV_noinc((SV *)h);
+  OUTPUT:
+    RETVAL
+
+SV *
+sw_opts(HV *opts)
+  CODE:
+    /* every field of the pr_sw_opts an option hash stands for (its defaults filled in) */
+    pr_sw_opts o;
+    HV *h = newHV();
+    fill_sw_opts(aTHX_ opts, &o);
+    hv_store(h, "a", 1, newSViv(o.a), 0);
+    hv_store(h, "b", 1, newSViv(o.b), 0);
+    hv_store(h, "o_del", 5, newSViv(o.o_del), 0);
+    hv_store(h, "e_del", 5, newSViv(o.e_del), 0);
+    hv_store(h, "o_ins", 5, newSViv(o.o_ins), 0);
+    hv_store(h, "e_ins", 5, newSViv(o.e_ins), 0);
+    hv_store(h, "w", 1, newSViv(o.w), 0);
+    hv_store(h, "pen_clip5", 9, newSViv(o.pen_clip5), 0);
+    hv_store(h, "pen_clip3", 9, newSViv(o.pen_clip3), 0);
+    hv_store(h, "zdrop", 5, newSViv(o.zdrop), 0);
+    hv_store(h, "min_score_per_base", 18, newSVnv(o.min_score_per_base), 0);
+    hv_store(h, "bin_size", 8, newSViv(o.bin_size), 0);
+    hv_store(h, "bin_length", 10, newSVnv(o.bin_length), 0);
+    hv_store(h, "drop_ratio", 10, newSVnv(o.drop_ratio), 0);
+    hv_store(h, "mask_level", 10, newSVnv(o.mask_level), 0);
+    hv_store(h, "mask_level_redun", 16, newSVnv(o.mask_level_redun), 0);
+    hv_store(h, "max_chain_gap", 13, newSViv(o.max_chain_gap), 0);
+    RETVAL = newRV_noinc((SV *)h);
   OUTPUT:
     RETVAL

@@ -18,6 +18,10 @@ package Prgpu;
 #   print Prgpu::fastq($_) for @res;            # bam2cns:453
 #   print Prgpu::chim_lines($_) for @res;       # bam2cns:488
 #
+# The resident stages (lrset_*, srset_load, seed_map_sampled, iter_upload_lrset, iter_launch,
+# iter_chim, iter_mask, lrset_commit) are plain XS functions driven by Prgpu::Stages
+# (lib/Prgpu/Stages.pm); bin/prgpu-proovread runs proovread's whole task loop over them.
+#
 # There is no CPU fallback: without a gfx950 device Context->new dies.
 
 use strict;
