@@ -87,7 +87,7 @@ enum SeedBufId {
     SI_TEXT, SI_CSTART, SI_CBLK, SI_LROFF, SI_KOFF, SI_KPOS, SI_KEXT, SI_CNT0,
     SB_SEQ = SI_CNT0 + 11, SB_OFF, SB_SCRATCH, SB_OUT, SB_NOUT, SB_STATUS, SB_NEXT, SB_PRE, SB_DENSE,
     SX_LRSEQ, SX_KEY0, SX_KEY1, SX_VAL0, SX_KC, SX_CNTPTR, SX_TEMP, SI_KSPLIT, SX_VAL1, SX_KCC, SX_KOFFC, SX_KCUR,
-    SB_DP, SI_TEXT4, SB_ORDER, SI_BLKFR, SD_COUNT
+    SB_DP, SI_TEXT4, SB_ORDER, SI_BLKFR, SB_OCC, SD_COUNT
 };
 // the resident long-read set: pools, the dense offsets of a commit, the commit's staging pools
 // (LS_RSEQ / LS_RQUAL: pr_lrset_snapshot's raw reads; LS_SRSAMP: pr_srset_sample's task sample)

@@ -26,6 +26,7 @@
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
 #include <utility>
@@ -35,6 +36,7 @@
 
 #include "../../include/prgpu.h"
 #include "err.h"
+#include "seed_chain.h"
 #include "seed_core.h"
 #include "seed_dev.h"
 
@@ -763,6 +765,8 @@ extern "C" int pr_seed_map_device_caps(const pr_seed_index *h, const pr_seed_opt
     // scratch is never cleared, so a result that depends on the fill is a read of stale scratch
     const char *fe = getenv("PRGPU_SCRATCH_FILL");
     const uint64_t fill = fe ? 0x0101010101010101ull * (uint64_t)(strtoul(fe, nullptr, 0) & 0xFF) : 0;
+    const char *chn = getenv("PRGPU_SEED_CHAIN");   // lane: every read chained by its lane (pr_seed_gpu_map's hook)
+    const bool lane_chain = (chn && !strcmp(chn, "lane")) || caps.hi;   // (texts beyond 2^32: seed_api.cpp map_plan)
     auto work = [&]() {
         std::vector<uint64_t> slab((size_t)(bytes / 8 + 1), fill);
         seedc::Scratch S = seedc::carve(reinterpret_cast<uint8_t *>(slab.data()), caps);
@@ -773,12 +777,19 @@ extern "C" int pr_seed_map_device_caps(const pr_seed_index *h, const pr_seed_opt
         S.htab_clean = true;
         std::vector<pr_seed_task> buf((size_t)caps.out);
         std::vector<uint64_t> big;
+        std::unique_ptr<seedc::ChainHost> lds(lane_chain ? nullptr : new seedc::ChainHost);
+        if (lds) std::memset(lds.get(), (int)(fill & 0xFF), sizeof(seedc::ChainHost));   // (LDS is never cleared either)
         for (;;) {
             const int i = next.fetch_add(1);
             if (i >= n_sr) break;
             const int len = (int)(sr_off[i + 1] - sr_off[i]);
             int n = 0, err = 0;
-            if (len > 0) err = seedc::map_read(V, *o, S, sr_seq + sr_off[i], len, i, buf.data(), caps.out, &n);
+            // the device's routing: reads without mem_flt_chained_seeds are chained from their
+            // occurrence list with the on-chip capacities (seed_chain.h), the lanes one after the
+            // other; one that outgrows them is mapped again as pass 2 maps it
+            if (len > 0)
+                err = lds ? seedc::map_read_chain(V, *o, S, *lds, sr_seq + sr_off[i], len, i, buf.data(), caps.out, &n)
+                          : seedc::map_read(V, *o, S, sr_seq + sr_off[i], len, i, buf.data(), caps.out, &n);
             // the device's later passes: the arrays that overflowed grown, up to 4 times
             seedc::Caps cg = caps;
             for (int pass = 3; pass <= 6 && err && !(err & (seedc::SC_OVER_LEN | seedc::SC_OVER_OUT)); ++pass) {

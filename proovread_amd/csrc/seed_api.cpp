@@ -386,6 +386,9 @@ struct SeedMap {   // one map call
     int64_t lanes2;            // pass 2's resident waves
     int64_t chunk;             // reads per chunk
     int32_t budget;            // pass 1's hit budget per read (lazy table; 0: none)
+    int64_t chain_waves, chain_waves2;   // seed_chain_kernel's resident waves, first and second geometry
+    int64_t occ_words;         // the occurrence pool's words
+    bool pool_full_said = false;
     // results so far: seeds per read, status, prefix of the seeds, flagged reads and their flags
     std::vector<int32_t> nout, st;
     std::vector<int64_t> pre;
@@ -426,6 +429,15 @@ void map_plan(SeedMap &M, const pr_seed_opts *o, const int64_t *sr_off) {
     K.n_sr = M.n_sr;
     K.caps = small;
     K.stride = seedc::scratch_bytes(small);
+    // the lane passes stop after the SMEMs and seed_chain_kernel chains their reads on chip;
+    // PRGPU_SEED_CHAIN=lane: every read chained by its lane, as before (A/B and test hook)
+    const char *chn = getenv("PRGPU_SEED_CHAIN");
+    // A text beyond 2^32 positions (configs[3] ranks) keeps the lane chaining: there nearly every
+    // read outgrows pass 1's hit table and is mapped by the by-wave passes, and the device memory
+    // peaks within a few GB of the card later in the task, so no pool is taken for it
+    K.chain = (chn && !strcmp(chn, "lane")) || caps.hi ? 0 : 1;
+    M.chain_waves = (int64_t)c->n_cu * seed_chain_waves_per_cu(0);
+    M.chain_waves2 = (int64_t)c->n_cu * seed_chain_waves_per_cu(1);
     const char *wpc = getenv("PRGPU_SEED_WAVES_PER_CU");   // tuning hook
     size_t fr = 0, tot = 0;
     (void)hipMemGetInfo(&fr, &tot);
@@ -448,6 +460,9 @@ void map_plan(SeedMap &M, const pr_seed_opts *o, const int64_t *sr_off) {
     M.chunk = seedp::out_chunk(ob ? std::max<int64_t>(1, atoll(ob)) << 20
                                   : seedp::out_budget((int64_t)fr, (int64_t)M.D[SB_OUT].cap),
                                (int64_t)caps.out * (int64_t)sizeof(pr_seed_task));
+    M.occ_words = K.chain ? seedp::occ_pool_words(std::min<int64_t>(M.chunk, M.n_sr), small.lazy != 0, (int64_t)fr,
+                                                  (int64_t)M.D[SB_OCC].cap)
+                          : 0;
 }
 
 // the call's buffers, the reads on the device (in_sb_seq: SB_SEQ holds them already), K's pointers
@@ -473,7 +488,7 @@ int map_buffers(SeedMap &M, const pr_seed_opts *o, const uint8_t *sr_seq, bool i
         (rc = D[SB_OUT].ensure((size_t)(std::min<int64_t>(M.chunk, n_sr) * slot_bytes + 16))) ||
         (rc = D[SB_NOUT].ensure((size_t)n_sr * 4 + 16)) || (rc = D[SB_STATUS].ensure((size_t)n_sr * 4 + 16)) ||
         (rc = D[SB_NEXT].ensure(256)) || (rc = D[SB_PRE].ensure(((size_t)n_sr + 1) * 8)) ||
-        (rc = D[SB_DENSE].ensure(sizeof(pr_seed_task))))
+        (rc = D[SB_DENSE].ensure(sizeof(pr_seed_task))) || (M.occ_words && (rc = D[SB_OCC].ensure((size_t)M.occ_words * 8))))
         return rc;
     K.sr_seq = D[SB_SEQ].as<uint8_t>();
     K.sr_off = D[SB_OFF].as<int64_t>();
@@ -482,6 +497,8 @@ int map_buffers(SeedMap &M, const pr_seed_opts *o, const uint8_t *sr_seq, bool i
     K.status = D[SB_STATUS].as<int32_t>();
     K.next = D[SB_NEXT].as<int32_t>();
     K.prof = reinterpret_cast<unsigned long long *>(D[SB_NEXT].as<uint8_t>() + 64);
+    // (next[1], next[2]: the chaining launches' counters; next[4..5]: the occurrence pool's cursor)
+    K.occ = seedc::OccPool{D[SB_OCC].as<uint64_t>(), reinterpret_cast<unsigned long long *>(K.next + 4), M.occ_words};
     HIPCHK(hipMemsetAsync(K.next, 0, 256, s));
     return 0;
 }
@@ -518,14 +535,26 @@ int pass1(SeedMap &M, int64_t r0, int64_t r1, std::vector<int32_t> &redo, seedp:
         start = 0;
     }
     HIPCHK(hipMemcpyAsync(K.next, &start, 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(K.next + 1, 0, 28, s));
     int e = seed_batch_launch(K, (void *)s);
     if (e) return set_error(PR_ERR_HIP, "seed kernel: %s", hipGetErrorString((hipError_t)e));
+    if ((e = seed_chain_launch(K, M.chain_waves, M.chain_waves2, (void *)s)))
+        return set_error(PR_ERR_HIP, "seed chaining kernel: %s", hipGetErrorString((hipError_t)e));
     if (r0 == 0) HIPCHK(hipEventRecord(M.c->ev[10], s));
     std::vector<int32_t> st1((size_t)(r1 - r0)), no1((size_t)(r1 - r0));
     if ((rc = download(st1.data(), D[SB_STATUS], (size_t)(r1 - r0), s, (size_t)r0)) ||
         (rc = download(no1.data(), D[SB_NOUT], (size_t)(r1 - r0), s, (size_t)r0)))
         return rc;
+    unsigned long long asked = 0;   // the pool words pass 1's reads asked for
+    if (K.chain) HIPCHK(hipMemcpyAsync(&asked, K.occ.cursor, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    // a full pool flags the reads beyond it SC_OVER_SEEDS like a true seed overflow: they are
+    // mapped by the later passes, exact but slower, so it is said once per map
+    if ((int64_t)asked > K.occ.cap && !M.pool_full_said) {
+        M.pool_full_said = true;
+        std::fprintf(stderr, "[seed] occurrence pool full: %lld reads asked for %llu words of %lld; the reads beyond it take the later passes\n",
+                     (long long)(r1 - r0), asked, (long long)K.occ.cap);
+    }
     for (int64_t i = r0; i < r1; ++i)
         if (st1[(size_t)(i - r0)]) {
             redo.push_back((int32_t)i);
@@ -548,8 +577,9 @@ int launch_pass(SeedMap &M, const char *name, bool by_wave, const seedc::Caps &c
     K.rlist = M.D[SB_PRE].as<int32_t>();
     K.n_list = (int64_t)reads.size();
     HIPCHK(hipMemcpyAsync(M.D[SB_PRE].p, reads.data(), reads.size() * 4, hipMemcpyHostToDevice, M.s));
-    HIPCHK(hipMemsetAsync(K.next, 0, 4, M.s));
-    const int e = by_wave ? seed_launch(K, (void *)M.s) : seed_batch_launch(K, (void *)M.s);
+    HIPCHK(hipMemsetAsync(K.next, 0, 32, M.s));
+    int e = by_wave ? seed_launch(K, (void *)M.s) : seed_batch_launch(K, (void *)M.s);
+    if (!e && !by_wave) e = seed_chain_launch(K, M.chain_waves, M.chain_waves2, (void *)M.s);
     if (e) return set_error(PR_ERR_HIP, "seed kernel (%s): %s", name, hipGetErrorString((hipError_t)e));
     return 0;
 }

@@ -4,6 +4,7 @@
 
 #include <vector>
 
+#include "seed_chain.h"
 #include "seed_core.h"
 
 namespace prgpu {
@@ -30,10 +31,16 @@ struct SeedDev {
     const int32_t *rlist;      // pass 2: the reads to map (n_list of them); null: 0 .. n_list
     int64_t n_list;
     int32_t batch;             // lazy kernel: reads a wave dequeues at a time = slices per wave (1..64; pass 1: 64)
+    seedc::OccPool occ;        // the lane phase's occurrence lists (seed_chain.h), the cursor zeroed per launch
+    int32_t chain;             // the lane phase hands reads without mem_flt_chained_seeds to seed_chain_kernel
+                               // (0: PRGPU_SEED_CHAIN=lane, every read chained by its lane)
 };
 
 int seed_launch(const SeedDev &D, void *stream);         // pass 2: one wave per read of rlist
 int seed_batch_launch(const SeedDev &D, void *stream);   // pass 1: 64 reads per wave, lane per read
+// the chaining of a lane pass's reads, one wave per read with the state in LDS (after seed_batch_launch)
+int seed_chain_launch(const SeedDev &D, int64_t waves, int64_t waves2, void *stream);
+int seed_chain_waves_per_cu(int second);   // resident waves per CU of its first / second geometry
 // pass 1's read order, costliest first: a per-read cost estimate (the summed occurrence counts of
 // its 12-mers, every second start) sorted descending -> order[0 .. n) (reads r0 .. r0 + n).
 // buf: seed_order_bytes(n) bytes of device scratch

@@ -15,6 +15,7 @@
 
 #include <rocprim/device/device_radix_sort.hpp>
 
+#include "seed_chain.h"
 #include "seed_core.h"
 #include "seed_dev.h"
 
@@ -964,10 +965,23 @@ __global__ void __launch_bounds__(64 * SEED_WAVES, SEED_MINB) seed_batch_kernel(
             seedc::Scratch S = seedc::carve(base + (int64_t)lane * D.stride, D.caps);
             S.htab_clean = HTAB_REUSE;
             int n = 0, err = my_err;
-            if (len > 0 && !err)
-                err = seedc::map_after_occ<LZ>(D.V, D.O, S, D.sr_seq + o, len, i, D.out + (int64_t)(i - D.out0) * D.caps.out,
-                                           D.caps.out, &n, D.prof ? lt : nullptr, lcnt,
-                                           D.dp ? D.dp + slot * (2 * 201 * 64) + lane : nullptr);
+            pr_seed_task *slots = D.out + (int64_t)(i - D.out0) * D.caps.out;
+            if (len > 0 && !err && D.chain && seedc::seed_flt_min_score(D.O, len) < 0) {
+                // bwa skips mem_flt_chained_seeds for this read: the lane stops after the SMEMs and
+                // hands over the occurrences mem_chain takes (n: their number, the list's first pool
+                // word at the head of the read's slots); seed_chain_kernel chains them on chip
+                const seedc::OccB<LZ> occ{&D.V, &S, D.sr_seq + o, len, lcnt};
+                const int nm = seedc::collect_intv(occ, S, D.O, D.sr_seq + o, len, err, D.prof ? lt : nullptr);
+                if (LZ) err |= S.lz[1];
+                int64_t w0 = 0;
+                if (!err) err = seedc::emit_occ<LZ>(D.O, S, nm, D.occ, &w0, &n);
+                if (LZ) err |= S.lz[1];
+                *reinterpret_cast<int64_t *>(slots) = w0;
+            } else if (len > 0 && !err) {
+                err = seedc::map_after_occ<LZ>(D.V, D.O, S, D.sr_seq + o, len, i, slots, D.caps.out, &n,
+                                               D.prof ? lt : nullptr, lcnt,
+                                               D.dp ? D.dp + slot * (2 * 201 * 64) + lane : nullptr);
+            }
             // a read whose hit table overflowed reports the hits it needs (the retry pass sizes
             // its slices from them: texts of 1 - 3 Gb give ~20-50 k hits per 150 bp read)
             D.n_out[i] = (my_err & seedc::SC_OVER_HITS) ? -my_hits
@@ -1102,6 +1116,84 @@ int seed_launch(const SeedDev &D, void *stream) {
         hipLaunchKernelGGL(seed_wave_kernel<1>, dim3((unsigned)blocks), dim3(64 * SEED_WAVES), 0, (hipStream_t)stream, D);
     else
         hipLaunchKernelGGL(seed_wave_kernel<4>, dim3((unsigned)blocks), dim3(64 * SEED_WAVES), 0, (hipStream_t)stream, D);
+    return (int)hipGetLastError();
+}
+
+// The chaining of a lane pass's reads (seed_chain.h chain_read): persistent waves take 64 reads at
+// a time and chain those the lane phase handed over, one after the other, the chaining state in
+// the workgroup's LDS (one wave a workgroup).  Two launches: the first geometry for every read; a
+// read that outgrows it is left for the second (its occurrence count negated, minus one), and
+// one that outgrows that too is flagged for the later passes.  Reads the lane phase chained
+// itself (mem_flt_chained_seeds reads, D.chain off) or flagged are left as they are.
+template <class LDS, bool SECOND>
+__global__ void __launch_bounds__(64) seed_chain_kernel(SeedDev D) {
+    __shared__ LDS L;
+    const int lane = threadIdx.x;
+    const int64_t nlim = D.rlist ? D.n_list : D.n_sr - D.out0;
+    unsigned long long ct[3] = {0ULL, 0ULL, 0ULL};   // chaining, mem_chain_flt, output
+    for (;;) {
+        int j0 = 0;
+        if (lane == 0) j0 = atomicAdd(D.next + (SECOND ? 2 : 1), 64);
+        j0 = __shfl(j0, 0, 64);
+        if (j0 >= nlim) {   // every wave reaches this: the grid drains
+            if (D.prof && lane == 0)
+                for (int k = 0; k < 3; ++k) atomicAdd(&D.prof[4 + 3 + k], ct[k] * 64ULL);   // (as lane-summed ticks)
+            break;
+        }
+        // a lane per read: which of the 64 are this launch's
+        int my_i = -1, my_n = 0, my_len = 0;
+        if (j0 + lane < nlim) {
+            const int i = D.rlist ? D.rlist[j0 + lane] : (int)(D.out0 + j0 + lane);
+            const int len = (int)(D.sr_off[i + 1] - D.sr_off[i]);
+            const int n = D.n_out[i];
+            if (len > 0 && D.status[i] == 0 && seedc::seed_flt_min_score(D.O, len) < 0 && (SECOND ? n < 0 : n > 0))
+                my_i = i, my_n = SECOND ? -n - 1 : n, my_len = len;
+        }
+        unsigned long long todo = __ballot(my_i >= 0);
+        while (todo) {
+            const int src = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const int i = __shfl(my_i, src, 64), n = __shfl(my_n, src, 64), len = __shfl(my_len, src, 64);
+            pr_seed_task *slots = D.out + (int64_t)(i - D.out0) * D.caps.out;
+            const int64_t w0 = *reinterpret_cast<const int64_t *>(slots);
+            __builtin_amdgcn_wave_barrier();   // (the list's word is read before any task is written)
+            const uint64_t *hfr = D.occ.w + w0;
+            int nt = 0;
+            const int err = seedc::chain_read(D.V, D.O, L, hfr, seedc::occ_ql(hfr, n), n, len, i, slots, D.caps.out, &nt,
+                                              D.prof && lane == 0 ? ct : nullptr, D.caps.seeds, D.caps.chains);
+            if (lane == 0) {
+                if (!SECOND && (err & (seedc::SC_OVER_SEEDS | seedc::SC_OVER_CHAINS))) {
+                    D.n_out[i] = -n - 1;   // the second geometry's
+                    *reinterpret_cast<int64_t *>(slots) = w0;
+                } else {
+                    D.n_out[i] = err ? 0 : nt;
+                    D.status[i] = err;
+                }
+            }
+        }
+    }
+}
+
+int seed_chain_waves_per_cu(int second) {
+    int nb = 0;
+    const hipError_t e =
+        second ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, seed_chain_kernel<seedc::ChainLdsLarge, true>, 64, 0)
+               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, seed_chain_kernel<seedc::ChainLdsSmall, false>, 64, 0);
+    return e != hipSuccess || nb < 1 ? 1 : nb;
+}
+
+// after pass 1 (or pass 1b by lane) over the same reads; D.next[1], D.next[2]: the two launches'
+// dequeue counters, zeroed
+int seed_chain_launch(const SeedDev &D, int64_t waves, int64_t waves2, void *stream) {
+    const int64_t n = D.rlist ? D.n_list : D.n_sr - D.out0;
+    if (n <= 0 || !D.chain) return 0;
+    const int64_t nb = (n + 63) / 64;
+    hipLaunchKernelGGL((seed_chain_kernel<seedc::ChainLdsSmall, false>), dim3((unsigned)std::max<int64_t>(1, std::min(waves, nb))),
+                       dim3(64), 0, (hipStream_t)stream, D);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL((seed_chain_kernel<seedc::ChainLdsLarge, true>), dim3((unsigned)std::max<int64_t>(1, std::min(waves2, nb))),
+                       dim3(64), 0, (hipStream_t)stream, D);
     return (int)hipGetLastError();
 }
 

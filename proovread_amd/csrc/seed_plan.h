@@ -7,6 +7,7 @@
 
 #include <algorithm>
 
+#include "seed_chain.h"
 #include "seed_core.h"
 
 namespace prgpu {
@@ -71,6 +72,19 @@ inline int64_t out_budget(int64_t free_bytes, int64_t have) {
 // reads per chunk: their output slabs (slot_bytes a read) within out_budget, a multiple of 64
 inline int64_t out_chunk(int64_t out_budget, int64_t slot_bytes) {
     return std::max<int64_t>(64, out_budget / slot_bytes / 64 * 64);
+}
+
+// The pool of the lane passes' occurrence lists (seed_chain.h), in 8-byte words: what the chunk's
+// reads hand over on average with room to spare (occ_words_per_read) plus one read's largest
+// list, within 8 GB (configs[1]'s 460 k reads: 2,330 words or 1,550 occurrences a read) and a sixteenth of the free device
+// memory, and at least that one list.  A read that finds the pool full is flagged and takes the
+// later passes, so a crowded device or a larger sample loses speed only.
+// have: the bytes SB_OCC already holds
+inline int64_t occ_pool_words(int64_t n_reads, bool lazy, int64_t free_bytes, int64_t have) {
+    const int64_t one = seedc::occ_words(seedc::OCC_MAX);
+    const int64_t want = n_reads * seedc::occ_words_per_read(lazy) + one;
+    const int64_t lim = std::min<int64_t>((int64_t)8 << 30, (free_bytes + have) / 16) / 8;
+    return std::max<int64_t>(one, std::min<int64_t>(want, lim));
 }
 
 // what pass 1 left of a chunk: the flagged reads, their flags or-ed, and the hit tables they
