@@ -364,6 +364,15 @@ int pr_sw_extension_kernels(pr_ctx *ctx, double *ms, int64_t *cells, int32_t *la
 /* Diagnostics: shader-clock cycles summed over waves of the packed CIGAR kernel's
  * phases in the last launch: [0] query masks, [1] DP, [2] backtrack, [3] CIGAR emit. */
 int pr_sw_phase_cycles(pr_ctx *ctx, int64_t *out4);
+/* Diagnostics: the route byte of each of the n tasks of the last single-seed launch (n must be
+ * the batch's task count).  Bits: 0x01 / 0x02 the left / right extension asked for the second
+ * band (w << 1); 0x08 / 0x10 the packed extension met an N on the left / right side and handed
+ * the side to the ring kernel; CIGAR pass, tasks outside the packed kernel (set only while the
+ * packed kernel is on): 0x40 band <= 40 ring, 0x80 band <= 80 ring, 0x04 general kernel (also
+ * set by a ring or packed kernel that hands its task on); 0x20 the CIGAR outgrew its slot
+ * (overflow pass).  Reads the bytes the launch left behind and adds no work to pr_sw_launch.
+ * PR_ERR_ARG without a launched resident batch, and in bwa mode (refilled every round). */
+int pr_sw_task_flags(pr_ctx *ctx, uint8_t *out, int64_t n);
 
 /* ------------------------------------------------------------------ */
 /* host seeding front end: `bwa-proovread index` + the seeding / chaining part

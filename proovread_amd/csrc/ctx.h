@@ -137,6 +137,7 @@ static_assert(SWB_CELLS == 24 && SWB_CIGOUT == 34 && SWB_CHAIN == 35 && SWB_COUN
 // the resident SW batch (sw_api.cpp)
 struct SwResident {
     bool loaded = false;
+    bool launched = false;      // a single-seed launch ran on the resident batch (SWB_XTRY holds its flags)
     int64_t n_task = 0, n_sr = 0, n_lr = 0;
     int qmax = 0;
     DevBuf buf[SWB_COUNT];

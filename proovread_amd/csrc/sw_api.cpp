@@ -67,6 +67,7 @@ static int sw_upload_impl(pr_ctx *c, const pr_sw_batch *b, const pr_seed_task *d
     SwResident &r = c->sw;
     hipStream_t s = c->stream;
     c->x_ready = c->x_pass = false;   // an exchange of the previous batch must not be consumed
+    r.launched = false;
     int qmax = 1;
     for (int i = 0; i < b->n_sr; ++i) {
         const int64_t l = b->sr_off[i + 1] - b->sr_off[i];
@@ -640,8 +641,12 @@ extern "C" int pr_sw_launch(pr_ctx *c, const pr_sw_opts *o) {
         }
     r.ext_ev.n = 0;
     r.ext_ev.dropped = 0;
+    r.launched = false;
     if (r.bwa) return bwa_launch(c, r, D, O, o, grid_w, grid_pk, grid_g, lds_glob);
-    if (r.n_task == 0) return 0;
+    if (r.n_task == 0) {
+        r.launched = true;
+        return 0;
+    }
     HIPCHK(hipMemcpyAsync(r.buf[SWB_CIGAT].p, r.buf[SWB_CIGSLOT].p, (size_t)r.n_task * 8, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipEventRecord(c->ev[2], s));
     int e = sw_launch_extend(D, O, c->n_cu * 16, grid_pk, (void *)s, &r.ext_ev);
@@ -676,6 +681,7 @@ extern "C" int pr_sw_launch(pr_ctx *c, const pr_sw_opts *o) {
     }
     r.n_overflow = (int64_t)sp[0];
     HIPCHK(hipEventRecord(c->ev[0], s));
+    r.launched = true;
     return 0;
 }
 
@@ -1273,6 +1279,19 @@ int sw_get_pipe_ptrs(pr_ctx *c, SwPtrs *p, bool regroup) {
     p->pass = p->strand + n1;
     p->n_task = n;
     p->task_off = (const int64_t *)r.buf[SWB_GLROFF].p;
+    return 0;
+}
+
+extern "C" int pr_sw_task_flags(pr_ctx *c, uint8_t *out, int64_t n) {
+    // the route byte of every task of the last single-seed launch (SWB_XTRY, bits in prgpu.h)
+    if (!c || (!out && n > 0) || n < 0) return pr_set_error(PR_ERR_ARG, "null arg");
+    SwResident &r = c->sw;
+    if (r.loaded && r.bwa) return pr_set_error(PR_ERR_ARG, "pr_sw_task_flags: bwa mode refills the flags every round");
+    if (!r.loaded || !r.launched) return pr_set_error(PR_ERR_ARG, "no launched resident SW batch (pr_sw_launch first)");
+    if (n != r.n_task) return pr_set_error(PR_ERR_ARG, "pr_sw_task_flags: n is not the batch's task count");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (n) HIPCHK(hipMemcpy(out, r.buf[SWB_XTRY].p, (size_t)n, hipMemcpyDeviceToHost));
     return 0;
 }
 

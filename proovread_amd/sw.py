@@ -57,6 +57,7 @@ def _setup(L):
     L.pr_sw_dominant_kernel.argtypes = [C.c_void_p, _abi.PD, _abi.P64]
     L.pr_sw_extension_kernels.argtypes = [C.c_void_p, _abi.PD, _abi.P64, _abi.P32]
     L.pr_sw_phase_cycles.argtypes = [C.c_void_p, _abi.P64]
+    L.pr_sw_task_flags.argtypes = [C.c_void_p, _abi.PU8, C.c_int64]
     L.pr_sw_cigar_total.argtypes = [C.c_void_p, _abi.P64, _abi.P64]
     L.pr_sw_aln_count.argtypes = [C.c_void_p, _abi.P64]
     L.pr_sw_bwa_stats.argtypes = [C.c_void_p, _abi.P32, _abi.P64, _abi.P64]
@@ -220,3 +221,17 @@ def phase_cycles(ctx: _abi.Context):
     out = (C.c_int64 * 4)()
     _abi.check(L.pr_sw_phase_cycles(ctx.h, out), "pr_sw_phase_cycles")
     return list(out)
+
+
+def task_flags(ctx: _abi.Context) -> np.ndarray:
+    """The route byte of every task of the last single-seed launch (pr_sw_task_flags:
+    1 / 2 left / right second band, 8 / 16 packed extension met an N, 0x40 / 0x80 / 4 CIGAR
+    class ring-40 / ring-80 / general, 0x20 overflow pass)."""
+    L = _abi.lib()
+    _setup(L)
+    nt = C.c_int64()
+    _abi.check(L.pr_sw_aln_count(ctx.h, C.byref(nt)), "pr_sw_aln_count")   # single-seed mode: the task count
+    n = nt.value
+    out = np.zeros(max(n, 1), np.uint8)
+    _abi.check(L.pr_sw_task_flags(ctx.h, _abi.ptr(out, C.c_uint8), n), "pr_sw_task_flags")
+    return out[:n]
