@@ -689,6 +689,15 @@ int pr_iter_mask_download(pr_ctx *ctx, uint8_t *masked);
 int pr_fastq4_scan(const uint8_t *data, int64_t n, int64_t *n_rec, int64_t *n_bases);
 int pr_fastq4_fill(const uint8_t *data, int64_t n, const uint8_t *table256, int64_t *starts, int64_t *off,
                    uint8_t *pool);
+/* names: of the n_rec records that start at starts[] (any subset, any order: a task's sample),
+   the names (the first word after '@') behind each other and their offsets name_off [n_rec + 1],
+   and the quality lines behind each other.  seq_len [n_rec]: the sequence lengths the caller
+   holds; the quality pool takes their sum, and a record whose sequence line has another length
+   is declined, so nothing is written past it.  names / qual NULL: the offsets alone, to size the
+   names pool by.  PR_ERR_ARG for a start that is no plain 4-line record of that length, or a
+   record with a '\r' (what the scan declines). */
+int pr_fastq4_names(const uint8_t *data, int64_t n, const int64_t *starts, const int64_t *seq_len, int64_t n_rec,
+                    int64_t *name_off, char *names, uint8_t *qual);
 
 /* final quality trimming: the windows `SeqFilter --trim-win mean,min` keeps
  * (proovread.cfg:152-155; bin/proovread:919-943), i.e. Fastq::Seq::qual_window
@@ -773,6 +782,41 @@ int pr_bam_decode_last_ms(pr_ctx *ctx, double *ms);
  * PR_ERR_ARG if the file is not coordinate-sorted.                                     */
 int pr_bam_index(const uint8_t *data, int64_t len, int n_threads, uint8_t **out, int64_t *out_len);
 void pr_buffer_free(void *p);
+/* The encoder, the decoder's inverse (bam_enc_kernels.hip): the alignments the last pr_iter_launch
+ * handed to the consensus, as BAM records.  Valid after a pr_iter_launch in bwa mode on a world-1
+ * batch (pr_iter_upload with seeds, pr_iter_upload_gpu_seeds, pr_iter_upload_lrset), while the
+ * hand-off and the SW batch are resident (as for pr_iter_handoff_order).  The output is one
+ * library-allocated stream (pr_buffer_free) of block_size-prefixed records: the long reads of the
+ * range in order, each read's records in hand-off order, i.e. the body of a coordinate-sorted BAM
+ * whose reference ids are the long reads' indices.  A record is what pr_sam_encode makes of the
+ * line pr_sw_sam prints for the alignment (MAPQ 60, or 0 with FLAG 0x100; one aux field, AS),
+ * except that SEQ comes from the resident nt4 reads: a base other than A, C, G, T is N on both
+ * strands, which is what the consensus read.  The names and qualities are uploaded by the first
+ * call after a launch and kept until the next launch or upload: pass the same pools for every
+ * range of one launch.
+ * PR_ERR_ARG: no resident bwa-mode iteration that was launched, an explicit-task batch (it has no
+ * FLAG column), sr_off differing from the batch's, a name of 0 or more than 254 bytes (l_read_name
+ * is a uint8), a range outside the reads, a pr_sw_upload / pr_sw_launch on the context since the
+ * pr_iter_launch (the hand-off no longer belongs to the SW batch).  PR_ERR_UNSUPPORTED: an owned
+ * batch (pr_iter_upload_owned; its wire records carry only the strand bit of FLAG).
+ * PR_ERR_CAPACITY: the hand-off of a read of the range failed (as pr_iter_download reports it), or
+ * no host memory for the stream.  Every refusal happens before anything is launched and leaves the
+ * context as it was.                                                                           */
+typedef struct pr_bam_export_in {
+    int32_t lr_first, lr_count;     /* long reads [first, first+count) of the resident iteration */
+    const int64_t *sr_off;          /* [n_sr+1] the task's short reads, batch order              */
+    const char *sr_names;           /* names pool (first word of the header line)                */
+    const int64_t *sr_name_off;     /* [n_sr+1]                                                  */
+    const uint8_t *sr_qual;         /* phred+33 in sr_off layout, or NULL (QUAL = 0xFF)          */
+} pr_bam_export_in;
+int pr_iter_export_bam(pr_ctx *ctx, const pr_bam_export_in *in, uint8_t **recs, int64_t *len, int64_t *n_records);
+/* the bytes pr_iter_export_bam would return for the range (the size pass alone), and the same per
+ * long read of the range (per_read [lr_count]): one call sizes every range of a task */
+int pr_iter_export_bam_bytes(pr_ctx *ctx, const pr_bam_export_in *in, int64_t *len);
+int pr_iter_export_bam_read_bytes(pr_ctx *ctx, const pr_bam_export_in *in, int64_t *per_read);
+/* milliseconds of the encoder's kernels (HIP events on the ctx stream) of the last
+ * pr_iter_export_bam / pr_iter_export_bam_bytes */
+int pr_bam_export_last_ms(pr_ctx *ctx, double *ms);
 
 /* ------------------------------------------------------------------ */
 /* siamaera (bin/siamaera; bin/proovread:923-933): reverse-complement self-alignments of a

@@ -433,6 +433,20 @@ def _native_bgzf(data: bytes, level: int = 6, threads: int = 0) -> bytes:
     return _take(L, C, p, n)
 
 
+def write_sorted_bam(path: str, refs: Sequence[Tuple[str, int]], bodies: Iterable[bytes], threads: int = 0) -> None:
+    """A coordinate-sorted BAM from record streams that are already in coordinate order (each a
+    run of block_size-prefixed records, the runs in order): the header `samtools sort` of this
+    package writes for these references (@HD SO:coordinate, @SQ), every stream BGZF-compressed
+    natively at the writer's level into blocks of its own, the EOF marker."""
+    text = "@HD\tVN:1.5\tSO:coordinate\n" + "".join(f"@SQ\tSN:{n}\tLN:{l}\n" for n, l in refs)
+    with open(path, "wb") as fh:
+        w = BamWriter(fh, Header(text, list(refs)))
+        for body in bodies:
+            if body:
+                fh.write(_native_bgzf(body, w.w.level, threads))
+        fh.write(EOF_BLOCK)
+
+
 def _set_sort_order(text: str, so: str) -> str:
     lines = text.splitlines()
     if lines and lines[0].startswith("@HD"):

@@ -81,6 +81,7 @@ class LoopConfig:
     keep_masked: bool = False              # LoopResult.masked: the last regular task's masked reads
     sam: Optional[str] = None              # --sam: alignments made elsewhere (mode sam, task read-sam)
     bam: Optional[str] = None              # --bam: the same as a coordinate-sorted BAM (mode bam, task read-bam)
+    keep_temporary: Optional[str] = None   # --keep-temporary-files: the prefix PRE of PRE.<task>.bam / .bam.bai / .fq
 
 
 class LongReads:
@@ -186,12 +187,14 @@ class ShortReads:
         self.data = data
         total = len(data)
         rec = _fastq4_native(data)
+        self.fastq4 = rec is not None
         if rec is not None:   # plain 4-line FASTQ: record starts, offsets and nt4 pool in one native pass
             starts, self.off, self.pool = rec
         else:                 # FASTA (multi-line) or irregular FASTQ: the record parser
             spans = list(seqchunker.records(data))
             starts = np.array([x for x, _ in spans], np.int64)
             seqs = [self._seq_of(data[x:e]) for x, e in spans]
+        self.starts = np.ascontiguousarray(starts, np.int64)   # (names_of reads the records again)
         self.n_chunks = max(1, chunk_number)
         csize = max(1, math.ceil(total / self.n_chunks)) if total else 1
         chunk_of = np.minimum(starts // csize, self.n_chunks - 1) if len(starts) else np.zeros(0, np.int64)
@@ -224,6 +227,7 @@ class ShortReads:
         chunk_of = np.minimum(starts // csize, self.n_chunks - 1)
         self.cfirst = np.searchsorted(chunk_of, np.arange(self.n_chunks + 1), side="left").astype(np.int64)
         self.pool, self.off, self.lengths = pool, off, lens
+        self.starts, self.fastq4 = starts, False
         return self
 
     @staticmethod
@@ -253,6 +257,38 @@ class ShortReads:
         parts = [self.pool[self.off[a]:self.off[b]] for a, b in ranges]
         return np.concatenate(parts) if parts else np.zeros(0, np.uint8)
 
+    def names_of(self, ranges: np.ndarray) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
+        """-> (names pool, name offsets [n + 1], quality pool or None) of the records in `ranges`
+        (sample_ranges' record ranges), in sample order: what a BAM record of a sampled read needs
+        besides its bases.  The name is the first word after '@' or '>'; the qualities are the
+        FASTQ quality lines behind each other (the reads' layout), None for FASTA.  Plain 4-line
+        FASTQ is one native pass (pr_fastq4_names); anything else goes through the record parser."""
+        rg = np.asarray(ranges, np.int64).reshape(-1, 2)
+        idx = np.concatenate([np.arange(a, b) for a, b in rg]) if len(rg) else np.zeros(0, np.int64)
+        if self.data is None:   # from_pool: the records "@sr<i>", no quality characters to give
+            enc = [b"sr%d" % i for i in idx]
+            pool, off = _pool(enc)
+            return pool, off, None
+        # (the native pass only where the input itself took it: the parser strips what it tolerates)
+        got = _fastq4_names_native(self.data, self.starts[idx], self.lengths[idx]) if self.fastq4 else None
+        if got is not None:
+            return got
+        ends = np.append(self.starts[1:], len(self.data))
+        names, quals = [], []
+        for i in idx:
+            rec = self.data[int(self.starts[i]):int(ends[i])]
+            lines = rec.split(b"\n")
+            names.append(lines[0][1:].split()[0] if lines[0][1:].split() else b"")
+            quals.append(lines[3].strip() if rec[:1] == b"@" and len(lines) > 3 else None)
+        pool, off = _pool(names)
+        if not quals or any(q is None for q in quals):
+            return pool, off, None
+        for i, nm, q in zip(idx, names, quals):   # (the quality pool has the reads' layout)
+            if len(q) != int(self.lengths[i]):
+                raise ValueError(f"short read {nm.decode(errors='replace')} (record {int(i)}): a quality line of {len(q)} "
+                                 f"for {int(self.lengths[i])} bases")
+        return pool, off, _pool(quals)[0]
+
     def sample(self, sc: Optional[Dict[str, int]]) -> Tuple[np.ndarray, np.ndarray]:
         """nt4 pool of the records SeqChunker writes for cov2seqchunker's parameters
         (None: every record), in stream order."""
@@ -280,6 +316,29 @@ def _fastq4_native(data: bytes):
     _abi.check(L.pr_fastq4_fill(data, len(data), NT4.ctypes.data, starts.ctypes.data, off.ctypes.data, pool.ctypes.data),
                "pr_fastq4_fill")
     return starts, off, pool
+
+
+def _fastq4_names_native(data: bytes, starts: np.ndarray, lengths: np.ndarray):
+    """(names pool, name offsets, quality pool) of the plain 4-line FASTQ records that start at
+    `starts` and hold sequences of `lengths` (pr_fastq4_names), or None when a start is no such
+    record (FASTA, multi-line, CR LF, blanks around the sequence)."""
+    from . import _abi
+    L = _abi.lib()
+    L.pr_fastq4_names.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]
+    st = np.ascontiguousarray(starts, np.int64)
+    ln = np.ascontiguousarray(lengths, np.int64)
+    if len(ln) != len(st):
+        raise ValueError("one length per record start")
+    off = np.zeros(len(st) + 1, np.int64)
+    if not data or L.pr_fastq4_names(data, len(data), st.ctypes.data, ln.ctypes.data, len(st), off.ctypes.data, None,
+                                     None) != 0:
+        return None
+    names = np.zeros(int(off[-1]) + 1, np.uint8)
+    qual = np.zeros(int(ln.sum()) + 1, np.uint8)
+    _abi.check(L.pr_fastq4_names(data, len(data), st.ctypes.data, ln.ctypes.data, len(st), off.ctypes.data,
+                                 names.ctypes.data, qual.ctypes.data), "pr_fastq4_names")
+    return names, off, qual
 
 
 # ---------------------------------------------------------------------------- device stages
@@ -349,10 +408,16 @@ class GpuStages:
                    "pr_srset_load")
 
     def task(self, task: str, sr: Optional[np.ndarray], sr_off: np.ndarray, params, bin_filter, comm=None,
-             exact: bool = False, mask_cfg=None, sr_ranges: Optional[np.ndarray] = None, dry: bool = False) -> TaskOut:
+             exact: bool = False, mask_cfg=None, sr_ranges: Optional[np.ndarray] = None, dry: bool = False,
+             keep=None) -> TaskOut:
         """One bwa-sr task on the resident set.  mask_cfg = (hcr-mask, min_sr_length) for the
         regular tasks, None for the finish task (which maps to the unmasked reads,
-        proovread:838-850); exact: the multi-GPU exact-parity layout."""
+        proovread:838-850); exact: the multi-GPU exact-parity layout (SURVEY.md §8e);
+        keep = (path prefix, names pool, name offsets, quality pool or None) of the task's short
+        reads (ShortReads.names_of): the task's alignments are left as PRE.<task>.bam and
+        .bam.bai (--keep-temporary-files, keep_alignments)."""
+        if keep is not None and (exact or (comm is not None and comm.world > 1)):
+            raise ValueError("keep: the alignments are exported from a world-1 batch only")
         from . import _abi, exact_shard as ex, iteration, mask, seed
         L = _abi.lib()
         seed._setup(L)
@@ -407,6 +472,8 @@ class GpuStages:
         self.device_ms += sd_ms
         tp.append(time.perf_counter())
         it.launch(opts, params)
+        if keep is not None:   # before the commit: lr_off and the ids are still the mapping reference's
+            self.keep_alignments(it, f"{keep[0]}.{task}", lr_off, *keep[1:])
         tp.append(time.perf_counter())
         out = TaskOut(n_tasks, [])
         if finish:
@@ -431,6 +498,42 @@ class GpuStages:
         self.last_part_ms["big_reads"] = it.handoff_stats(counts=False).big_reads   # reads sorted through HBM
         self.last_iteration = it   # the task's consensus outputs stay readable (tests, drivers)
         return out
+
+    EXPORT_RANGE_BYTES = 1 << 30   # a range's records on the device and on their way to the file
+
+    def keep_alignments(self, it, path: str, lr_off: np.ndarray, names, name_off, qual) -> int:
+        """The launched iteration's alignments as `path`.bam (bamio.write_sorted_bam: the header
+        the `samtools sort` drop-in writes, the records of Iteration.export_bam, BGZF at the
+        drop-in's level, its EOF marker) and `path`.bam.bai (pr_bam_index).  The records are
+        exported in ranges of long reads of at most EXPORT_RANGE_BYTES each, cut from one size
+        pass over the batch (pr_iter_export_bam_read_bytes); a read whose records alone exceed
+        that is a range of its own.  -> records."""
+        from . import bamio
+        n_lr = len(lr_off) - 1
+        refs = [(i, int(lr_off[k + 1] - lr_off[k])) for k, i in enumerate(self.ids[:n_lr])]
+        per_read = it.export_bam_read_bytes(names, name_off, qual) if n_lr else np.zeros(0, np.int64)
+        cuts, at = [0], 0
+        for k in range(n_lr):
+            if k > cuts[-1] and at + int(per_read[k]) > self.EXPORT_RANGE_BYTES:
+                cuts.append(k)
+                at = 0
+            at += int(per_read[k])
+        cuts.append(n_lr)
+        st = {"records": 0, "ms": it.export_ms() if n_lr else 0.0}
+
+        def bodies():
+            for a, b in zip(cuts, cuts[1:]):
+                if b > a and int(per_read[a:b].sum()):
+                    body = it.export_bam(names, name_off, qual, a, b - a)
+                    st["ms"] += it.export_ms()
+                    st["records"] += it.last_export_records
+                    yield body
+
+        bamio.write_sorted_bam(path + ".bam", refs, bodies())
+        bamio.index_bam(path + ".bam")
+        self.device_ms += st["ms"]
+        self.last_export_ms = round(st["ms"], 2)
+        return st["records"]
 
     def external_alignments(self, task: str, path: str, params) -> TaskOut:
         """read-sam / read-bam (bin/proovread:718-736): the consensus of every long read over
@@ -534,6 +637,20 @@ Comm = TorchComm
 
 
 # ---------------------------------------------------------------------------- the loop
+def keep_refused(cfg: LoopConfig, world: int) -> None:
+    """--keep-temporary-files with ranks or in the exact-parity layout: refused at start-up (an
+    owned batch's alignments carry only the strand bit of their FLAG)."""
+    if cfg.keep_temporary and (world > 1 or cfg.exact_layout):
+        raise ValueError("--keep-temporary-files runs on one GPU in the default layout: the alignments are "
+                         "exported from a world-1 batch (no ranks, no exact-parity layout)")
+
+
+def _write_task_fq(pre: str, task: str, reads: LongReads) -> None:
+    """PRE.<task>.fq: the long reads as the task left them (bin/proovread:965-971 keeps them)."""
+    with open(f"{pre}.{task}.fq", "w") as f:
+        f.write(reads.fastq())
+
+
 def mode_of(cfg: LoopConfig) -> Optional[str]:
     """bin/proovread:628-632: --bam selects mode bam, --sam mode sam, whatever --mode says;
     otherwise --mode, or None (by short-read length, proovread:636-642)."""
@@ -551,6 +668,7 @@ def run(lr_records: Sequence[Tuple[str, bytes, Optional[bytes]]], sr_data: bytes
     With `comm` (world > 1) every rank calls run() on the same inputs and gets the same
     result; the work is split as Comm describes.  n_tasks in the log is the rank's share."""
     cfg = cfg or LoopConfig()
+    keep_refused(cfg, comm.world if comm is not None else 1)
     stages = stages or GpuStages()
     srs = ShortReads(sr_data)
     min_sr = cfg.min_sr_length or (int(srs.lengths.min()) if len(srs.lengths) else 200)
@@ -567,6 +685,8 @@ def run(lr_records: Sequence[Tuple[str, bytes, Optional[bytes]]], sr_data: bytes
         if hasattr(stages, "load_short_reads") and len(srs.lengths):
             stages.load_short_reads(srs)
         log.append(TaskLog("read-long"))
+        if cfg.keep_temporary:
+            _write_task_fq(cfg.keep_temporary, "read-long", reads)
         tasks = tasks[1:]
     chim, last_masked, tlog = run_tasks(stages, srs, tasks, cfg, mode, min_sr, bool(ids), comm)
     log += tlog
@@ -612,6 +732,8 @@ def run_tasks(stages, srs: ShortReads, tasks: List[str], cfg: LoopConfig, mode: 
             r = stages.external_alignments(task, path, params) if have_reads else TaskOut(0, [])
             ent.n_tasks = r.n_tasks
             chim += r.chim
+            if cfg.keep_temporary and have_reads:
+                _write_task_fq(cfg.keep_temporary, task, stages.reads())
             ent.wall_ms = round((time.perf_counter() - t_task) * 1e3, 1)
             if dev0 is not None:
                 ent.device_ms = round(stages.device_ms - dev0, 1)
@@ -649,9 +771,15 @@ def run_tasks(stages, srs: ShortReads, tasks: List[str], cfg: LoopConfig, mode: 
         if finish and cfg.keep_masked:
             last_masked = stages.masked()
         ent.pre_ms = round((time.perf_counter() - t_task) * 1e3, 2)   # (host: sampling and set-up)
+        kw = {}
+        if cfg.keep_temporary and have_reads:   # the task's alignments as PRE.<task>.bam (+ .bai)
+            keep_refused(cfg, comm.world if comm is not None else 1)
+            kw["keep"] = (cfg.keep_temporary, *srs.names_of(ranges))
         r = stages.task(task, sr, sr_off, params, binf, comm, multi or cfg.exact_layout,
-                        None if finish else (hcr_mask_for(task), min_sr), sr_ranges=ranges) if have_reads \
+                        None if finish else (hcr_mask_for(task), min_sr), sr_ranges=ranges, **kw) if have_reads \
             else TaskOut(0, [])
+        if cfg.keep_temporary and have_reads:
+            _write_task_fq(cfg.keep_temporary, task, stages.reads())
         ent.n_tasks = r.n_tasks
         lines, bpt, bpn = r.chim, r.bpt, r.bpn
         if multi:
@@ -727,7 +855,12 @@ def parse_args(argv: Optional[Sequence[str]] = None):
     ap.add_argument("-t", "--threads", type=int, default=0)
     ap.add_argument("--siamaera", action="store_true",
                     help="pass the trimmed reads through the siamaera stage (the reference's default)")
+    ap.add_argument("--keep-temporary-files", action="store_true",
+                    help="leave PRE.<task>.bam, .bam.bai and .fq of every task (one GPU)")
     a = ap.parse_args(argv)
+    if a.keep_temporary_files and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--keep-temporary-files runs on one GPU (WORLD_SIZE > 1: the ranks' owned batches carry only the "
+                 "strand bit of FLAG)")
     if not (a.short_reads or a.sam or a.bam):
         ap.error("either -s/--short-reads or --sam / --bam is required")
     for opt, f in (("--sam", a.sam), ("--bam", a.bam)):
@@ -757,7 +890,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         lrs += list(zip(names, seqs, quals))
     sr_data = b"".join(open(f, "rb").read() for f in a.short_reads)
     cfg = LoopConfig(coverage=a.coverage, sampling=not a.no_sampling, seed_threads=a.threads, mode=a.mode,
-                     sam=a.sam, bam=a.bam)
+                     sam=a.sam, bam=a.bam, keep_temporary=a.pre if a.keep_temporary_files else None)
     comm, rank = None, 0
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         from . import _abi

@@ -6,6 +6,10 @@
 // The host's share: one pre-pass over the records' sizes (the offsets the kernels index by, and
 // the three size errors of bam_codec.cpp:491-500), the scans over reference ids and long reads
 // (a few thousand entries) between the passes, and Perl's numification of AS:Z scores.
+//
+// And the encoder's (bam_enc_kernels.hip): pr_iter_export_bam, pr_iter_export_bam_bytes and
+// pr_bam_export_last_ms -- the refusals, the upload of the names and qualities, the passes over
+// the resident hand-off, the download of the record stream.
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -13,6 +17,8 @@
 #include "ctx.h"
 #include "bam_core.h"
 #include "bam_dev.h"
+#include "bam_enc_core.h"
+#include "bam_enc_dev.h"
 
 using namespace prgpu::bam;
 
@@ -334,5 +340,220 @@ extern "C" int pr_cns_resident_aln_count(pr_ctx *c, int64_t *n_aln, int64_t *aln
 extern "C" int pr_bam_decode_last_ms(pr_ctx *c, double *ms) {
     if (!c || !ms) return pr_set_error(PR_ERR_ARG, "null arg");
     *ms = c->ms_bam;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// the encoder: the resident hand-off as BAM records
+namespace {
+
+struct EncEvents {
+    hipEvent_t ev[4] = {};
+    ~EncEvents() {
+        for (auto &e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+// the record stream's device buffer is not held past the call that made it (up to a GiB per range)
+struct ReleaseOnExit {
+    DevBuf &b;
+    ~ReleaseOnExit() { b.release(); }
+};
+
+// The refusals, the uploads (once per launch), the FLAG scatter and the size pass of the range:
+// D is ready for the write pass, *total the bytes of the range's records.
+int export_prepare(pr_ctx *c, const pr_bam_export_in *in, BamEncDev &D, int64_t *total, EncEvents &E) {
+    if (!c || !in) return pr_set_error(PR_ERR_ARG, "null arg");
+    if (c->pipe && c->own)
+        return pr_set_error(PR_ERR_UNSUPPORTED, "BAM export: an owned batch carries only the strand bit of FLAG");
+    if (!c->pipe || !c->ho_done)
+        return pr_set_error(PR_ERR_ARG, "BAM export: no resident bwa-mode iteration (pr_iter_launch first)");
+    SwResident &r = c->sw;
+    if (!r.loaded || c->ho_sw_gen != r.gen)   // a pr_sw_upload / pr_sw_launch of its own since: other pools under the old hand-off
+        return pr_set_error(PR_ERR_ARG, "BAM export: the SW batch was uploaded or launched again after the hand-off "
+                                        "(pr_iter_launch first)");
+    if (!r.bwa)
+        return pr_set_error(PR_ERR_ARG, "BAM export: an explicit-task batch has no FLAG column (bwa mode only)");
+    if (!in->sr_off || !in->sr_names || !in->sr_name_off) return pr_set_error(PR_ERR_ARG, "BAM export: null pools");
+    if (in->lr_first < 0 || in->lr_count < 0 || (int64_t)in->lr_first + in->lr_count > c->n_lr)
+        return set_error(PR_ERR_ARG, "BAM export: reads [%d, %d + %d) outside the batch's %d", in->lr_first, in->lr_first,
+                         in->lr_count, c->n_lr);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t n_sr = (size_t)r.n_sr;
+    DevBuf *B = c->eb;
+    int rc;
+    if (c->eb_sr_gen != r.gen) {   // the batch's offsets, downloaded once per SW batch
+        c->eb_sr_gen = -1;
+        c->eb_sr_off.assign(n_sr + 1, 0);
+        HIPCHK(hipMemcpyAsync(c->eb_sr_off.data(), r.buf[SWB_SR_OFF].p, (n_sr + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        c->eb_sr_gen = r.gen;
+    }
+    const std::vector<int64_t> &batch_off = c->eb_sr_off;
+    if (std::memcmp(batch_off.data(), in->sr_off, (n_sr + 1) * 8) != 0)
+        return pr_set_error(PR_ERR_ARG, "BAM export: sr_off differs from the resident batch's short reads");
+    const bool fill = c->eb_gen != c->iter_gen || c->eb_names_key != (const void *)in->sr_names ||
+                      c->eb_qual_key != (const void *)in->sr_qual;
+    if (fill) {
+        if (in->sr_name_off[0] < 0) return pr_set_error(PR_ERR_ARG, "BAM export: sr_name_off must start at or after 0");
+        for (size_t i = 0; i < n_sr; ++i) {
+            const int64_t l = in->sr_name_off[i + 1] - in->sr_name_off[i];
+            if (l < 1 || l > 254)
+                return set_error(PR_ERR_ARG, "BAM export: the name of short read %zu (%.*s%s) has %lld bytes: 1 to 254 fit l_read_name",
+                                 i, (int)(l > 32 ? 32 : (l > 0 ? l : 0)), in->sr_names + in->sr_name_off[i], l > 32 ? "..." : "",
+                                 (long long)l);
+        }
+    }
+    std::memset(&D, 0, sizeof D);
+    D.lr_first = in->lr_first;
+    D.lr_count = in->lr_count;
+    D.aln_off = c->cb[CB_ALN_OFF].as<int64_t>();
+    // the range's alignments, and the hand-off's error flags of its reads: a read whose hand-off
+    // failed has no order to export (pr_iter_download reports the same flags)
+    int64_t a[2] = {0, 0};
+    std::vector<int32_t> err((size_t)in->lr_count + 1, 0);
+    HIPCHK(hipMemcpyAsync(&a[0], D.aln_off + in->lr_first, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&a[1], D.aln_off + in->lr_first + in->lr_count, 8, hipMemcpyDeviceToHost, s));
+    if (in->lr_count)
+        HIPCHK(hipMemcpyAsync(err.data(), c->pb[PB_ERR].as<int32_t>() + in->lr_first, (size_t)in->lr_count * 4,
+                              hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int32_t i = 0; i < in->lr_count; ++i)
+        if (err[(size_t)i])
+            return set_error(PR_ERR_CAPACITY, "BAM export: the hand-off of long read %d failed (code %d)", in->lr_first + i,
+                             err[(size_t)i]);
+    if (a[0] < 0 || a[1] < a[0] || a[1] > r.n_aln) return pr_set_error(PR_ERR_ARG, "BAM export: the hand-off's offsets are not those of this batch");
+    for (auto &e : E.ev) HIPCHK(hipEventCreate(&e));
+    D.g0 = a[0];
+    D.n = a[1] - a[0];
+    SwPtrs sp;
+    if ((rc = sw_get_pipe_ptrs(c, &sp, false))) return rc;
+    D.a_pos = c->cb[CB_POS].as<int32_t>();
+    D.a_score = c->cb[CB_SCORE].as<double>();
+    D.a_lseq = c->cb[CB_LSEQ].as<int32_t>();
+    D.a_ncig = c->cb[CB_NCIG].as<int32_t>();
+    D.a_task = c->pb[PB_ORDER].as<int32_t>();
+    D.task_off = sp.task_off;
+    D.t_sr = sp.t_sr;
+    D.strand = sp.strand;
+    D.cig_at = sp.cig_at;
+    D.glist = r.buf[SWB_GLIST].as<int32_t>();
+    D.cig = sp.cig;
+    D.sr = sp.sr;
+    D.sr_off = sp.sr_off;
+    D.alist = r.buf[SWB_ALIST].as<int32_t>();
+    D.aflag = r.buf[SWB_AFLAG].as<int32_t>();
+    D.n_sam = r.n_aln;
+    const size_t n1 = (size_t)D.n + 1, tb = bam_enc_temp_bytes(D.n);
+    if (fill) {
+        c->eb_gen = -1;
+        const size_t nb = (size_t)in->sr_name_off[n_sr] - (size_t)in->sr_name_off[0];
+        // (name offsets as given: the pool is uploaded from its first used byte, the offsets rebased)
+        std::vector<int64_t> noff(n_sr + 1);
+        for (size_t i = 0; i <= n_sr; ++i) noff[i] = in->sr_name_off[i] - in->sr_name_off[0];
+        if ((rc = upload(B[EB_NAMES], (const uint8_t *)in->sr_names + in->sr_name_off[0], nb, s)) ||
+            (rc = upload(B[EB_NAME_OFF], noff.data(), n_sr + 1, s)) ||
+            (in->sr_qual && (rc = upload(B[EB_QUAL], in->sr_qual, (size_t)batch_off[n_sr], s))) ||
+            (rc = B[EB_FLAG].ensure(((size_t)r.n_task + 1) * 2)))
+            return rc;
+        HIPCHK(hipStreamSynchronize(s));   // (noff leaves scope)
+    }
+    if ((rc = B[EB_LR].ensure(n1 * 4)) || (rc = B[EB_J].ensure(n1 * 4)) || (rc = B[EB_SIZE].ensure(n1 * 8)) ||
+        (rc = B[EB_OFF].ensure(n1 * 8)) || (rc = B[EB_TEMP].ensure(tb)))
+        return rc;
+    D.flag_by_task = B[EB_FLAG].as<uint16_t>();
+    D.names = B[EB_NAMES].as<uint8_t>();
+    D.name_off = B[EB_NAME_OFF].as<int64_t>();
+    D.qual = in->sr_qual ? B[EB_QUAL].as<uint8_t>() : nullptr;
+    D.e_lr = B[EB_LR].as<int32_t>();
+    D.e_j = B[EB_J].as<int32_t>();
+    D.e_size = B[EB_SIZE].as<int64_t>();
+    D.e_off = B[EB_OFF].as<int64_t>();
+    HIPCHK(hipEventRecord(E.ev[0], s));
+    if (fill) HIPCHK((hipError_t)bam_enc_flag_pass(D, (void *)s));
+    HIPCHK((hipError_t)bam_enc_size_pass(D, B[EB_OFF].as<int64_t>(), B[EB_TEMP].p, tb, (void *)s));
+    HIPCHK(hipEventRecord(E.ev[1], s));
+    HIPCHK(hipMemcpyAsync(total, D.e_off + D.n, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    if (fill) {
+        c->eb_gen = c->iter_gen;
+        c->eb_names_key = in->sr_names;
+        c->eb_qual_key = in->sr_qual;
+    }
+    float ms = 0.f;
+    c->ms_bam_enc = hipEventElapsedTime(&ms, E.ev[0], E.ev[1]) == hipSuccess ? ms : 0.f;
+    return 0;
+}
+
+}   // namespace
+
+extern "C" int pr_iter_export_bam_bytes(pr_ctx *c, const pr_bam_export_in *in, int64_t *len) {
+    if (!len) return pr_set_error(PR_ERR_ARG, "null arg");
+    BamEncDev D;
+    EncEvents E;
+    return export_prepare(c, in, D, len, E);
+}
+
+extern "C" int pr_iter_export_bam_read_bytes(pr_ctx *c, const pr_bam_export_in *in, int64_t *per_read) {
+    if (!per_read) return pr_set_error(PR_ERR_ARG, "null arg");
+    BamEncDev D;
+    EncEvents E;
+    int64_t total = 0;
+    int rc = export_prepare(c, in, D, &total, E);
+    if (rc || in->lr_count == 0) return rc;
+    DevBuf &rb = c->eb[EB_READ_BYTES];
+    if ((rc = rb.ensure((size_t)in->lr_count * 8))) return rc;
+    HIPCHK((hipError_t)bam_enc_read_bytes(D, rb.as<int64_t>(), (void *)c->stream));
+    HIPCHK(hipMemcpyAsync(per_read, rb.p, (size_t)in->lr_count * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int pr_iter_export_bam(pr_ctx *c, const pr_bam_export_in *in, uint8_t **recs, int64_t *len, int64_t *n_records) {
+    if (!recs || !len) return pr_set_error(PR_ERR_ARG, "null arg");
+    *recs = nullptr;
+    *len = 0;
+    BamEncDev D;
+    EncEvents E;
+    int64_t total = 0;
+    int rc = export_prepare(c, in, D, &total, E);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    DevBuf &out = c->eb[EB_OUT];
+    ReleaseOnExit out_guard{out};
+    if ((rc = out.ensure((size_t)total + 16))) return rc;
+    D.out = out.as<uint8_t>();
+    HIPCHK(hipEventRecord(E.ev[2], s));
+    HIPCHK((hipError_t)bam_enc_write_pass(D, (void *)s));
+    HIPCHK(hipEventRecord(E.ev[3], s));
+    uint8_t *h = (uint8_t *)std::malloc(total ? (size_t)total : 1);
+    if (!h) {
+        (void)hipStreamSynchronize(s);   // (the write pass, before its buffer goes)
+        return set_error(PR_ERR_CAPACITY, "BAM export: no host memory for %lld bytes of records: export fewer reads per call",
+                         (long long)total);
+    }
+    hipError_t e = total ? hipMemcpyAsync(h, out.p, (size_t)total, hipMemcpyDeviceToHost, s) : hipSuccess;
+    const hipError_t e2 = hipStreamSynchronize(s);   // (also after a failed copy: the write pass still runs)
+    if (e == hipSuccess) e = e2;
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) {
+        std::free(h);
+        return set_error(PR_ERR_HIP, "BAM export: %s", hipGetErrorString(e));
+    }
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, E.ev[2], E.ev[3]) == hipSuccess) c->ms_bam_enc += ms;
+    *recs = h;
+    *len = total;
+    if (n_records) *n_records = D.n;
+    return 0;
+}
+
+extern "C" int pr_bam_export_last_ms(pr_ctx *c, double *ms) {
+    if (!c || !ms) return pr_set_error(PR_ERR_ARG, "null arg");
+    *ms = c->ms_bam_enc;
     return 0;
 }

@@ -113,6 +113,11 @@ enum PipeBufId {
 };
 static_assert(PB_ORDER == 10, "pr_mem_stats and PRGPU_MEM_TRACE report the index");
 
+// the BAM export (pr_iter_export_bam): the FLAG column by SW task, the call's uploads (names, their
+// offsets, qualities), per exported alignment its long read, grouped index, record size and offset,
+// the scan's scratch, the record stream, the bytes of each read's records
+enum BamEncBufId { EB_FLAG, EB_NAMES, EB_NAME_OFF, EB_QUAL, EB_LR, EB_J, EB_SIZE, EB_OFF, EB_TEMP, EB_OUT, EB_READ_BYTES, EB_COUNT };
+
 // the SW stage's buffers (sw_api.cpp); from SWB_CHAIN on: bwa mode (aln_kernels.hip)
 enum SwBufId {
     SWB_SR, SWB_SR_OFF, SWB_LR, SWB_LR_OFF, SWB_T_SR, SWB_T_LR, SWB_T_STRAND, SWB_T_QBEG, SWB_T_RBEG, SWB_T_SLEN,
@@ -138,6 +143,7 @@ static_assert(SWB_CELLS == 24 && SWB_CIGOUT == 34 && SWB_CHAIN == 35 && SWB_COUN
 struct SwResident {
     bool loaded = false;
     bool launched = false;      // a single-seed launch ran on the resident batch (SWB_XTRY holds its flags)
+    int64_t gen = 0;            // counts uploads and launches: what was derived from a launch names the gen it saw
     int64_t n_task = 0, n_sr = 0, n_lr = 0;
     int qmax = 0;
     DevBuf buf[SWB_COUNT];
@@ -190,6 +196,14 @@ struct pr_ctx {
     float last_ms = 0.f;
     std::vector<int64_t> aln_off_host;   // the resident batch's alignment offsets (pr_cns_upload / pr_cns_upload_bam)
     float ms_bam = 0.f;                  // decode kernels of the last pr_cns_upload_bam / pr_bam_decode_alns_gpu
+    // the BAM export of the resident iteration (bam_api.cpp)
+    DevBuf eb[EB_COUNT];
+    float ms_bam_enc = 0.f;              // encoder kernels of the last pr_iter_export_bam / _bytes
+    int64_t iter_gen = 0;                // counts iteration uploads and launches: the export's uploads belong to one
+    int64_t eb_gen = -1;                 // the iter_gen EB_FLAG / EB_NAMES / EB_NAME_OFF / EB_QUAL were filled for
+    const void *eb_names_key = nullptr, *eb_qual_key = nullptr;   // and the host pools they were filled from
+    std::vector<int64_t> eb_sr_off;      // the SW batch's short-read offsets on the host, of sw.gen eb_sr_gen
+    int64_t eb_sr_gen = -1;
     // SW -> consensus pipeline (pr_iter_*)
     bool pipe = false;
     bool pipe_ref_ascii = false;   // pr_iter_batch.ref_seq given: consensus reference in CB_REF_SEQ
@@ -197,6 +211,7 @@ struct pr_ctx {
     DevBuf pb[PB_COUNT];
     handp::Plan ho;              // the hand-off's sort plan (explicit tasks: at upload; bwa mode: at launch)
     bool ho_done = false;        // a hand-off ran on this batch (pr_iter_handoff_stats / _order)
+    int64_t ho_sw_gen = -1;      // ... over the SW launch of this sw.gen (the BAM export reads both)
     std::vector<int32_t> own_cnt_host;   // owned batch: received alignments per long read
     float ms_pipe = 0.f, ms_cns = 0.f;
     // SW resident batch

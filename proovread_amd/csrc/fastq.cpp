@@ -64,3 +64,25 @@ extern "C" int pr_fastq4_fill(const uint8_t *d, int64_t n, const uint8_t *table2
     }
     return 0;
 }
+
+extern "C" int pr_fastq4_names(const uint8_t *d, int64_t n, const int64_t *starts, const int64_t *seq_len, int64_t n_rec,
+                               int64_t *name_off, char *names, uint8_t *qual) {
+    if (!d || !name_off || n_rec < 0 || (n_rec && (!starts || !seq_len)) || n <= 0) return PR_ERR_ARG;
+    int64_t o = 0, q = 0, s0, s1, next;
+    name_off[0] = 0;
+    for (int64_t r = 0; r < n_rec; ++r) {
+        const int64_t p = starts[r];
+        if (p < 0 || p >= n || !record(d, n, p, s0, s1, next)) return PR_ERR_ARG;
+        // what the scan declines is declined here: a '\r' in the record; and the sequence must be as
+        // long as the caller holds it (its quality pool is sized by that)
+        if (s1 - s0 != seq_len[r] || memchr(d + p, '\r', (size_t)(next - p))) return PR_ERR_ARG;
+        int64_t e = p + 1;   // the first word of the header line
+        while (e < s0 - 1 && d[e] != ' ' && d[e] != '\t') ++e;
+        if (names) memcpy(names + o, d + p + 1, (size_t)(e - p - 1));
+        o += e - p - 1;
+        name_off[r + 1] = o;
+        if (qual) memcpy(qual + q, d + next - 1 - (s1 - s0), (size_t)(s1 - s0));
+        q += s1 - s0;
+    }
+    return 0;
+}

@@ -56,6 +56,8 @@ int iter_upload(pr_ctx *c, const pr_iter_batch *b, bool gpu_seeds, const uint8_t
     c->cns_launched = false;
     c->iter_masked = false;
     c->own = false;
+    ++c->iter_gen;
+    for (auto &x : c->eb) x.release();   // a BAM export's pools belong to the batch they were made for
     hipStream_t s = c->stream;
     c->n_lr = n;
     c->n_aln = sb.n_task;
@@ -131,6 +133,7 @@ static int binfilter_setup(pr_ctx *c, PipeDev &P, int64_t n_task, const int64_t 
 extern "C" int pr_iter_launch(pr_ctx *c, const pr_sw_opts *o, const pr_cns_params *p) {
     if (!c || !o || !p) return set_error(PR_ERR_ARG, "null arg");
     if (!c->pipe) return set_error(PR_ERR_ARG, "no resident iteration batch (pr_iter_upload first)");
+    ++c->iter_gen;
     int rc;
     SwPtrs sp;
     if (c->own) {   // owned batch: the SW and the exchange ran before (ev[0]: the exchange's start)
@@ -208,6 +211,7 @@ extern "C" int pr_iter_launch(pr_ctx *c, const pr_sw_opts *o, const pr_cns_param
     int e = pipe_launch(P, grid, (void *)c->stream, c->pipe_sort_cap * 8, ho.n_big ? &G : nullptr);
     if (e) return set_error(PR_ERR_HIP, "pipe kernels: %s", hipGetErrorString((hipError_t)e));
     c->ho_done = true;
+    c->ho_sw_gen = c->sw.gen;
     return pr_cns_launch(c, p);
 }
 

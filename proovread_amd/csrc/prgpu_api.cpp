@@ -135,6 +135,7 @@ extern "C" int pr_ctx_create(int device, pr_ctx **out) {
     tag(c->sd, SD_COUNT, "seed");
     tag(c->xb, XB_COUNT, "xchg");
     tag(c->ls, LS_COUNT, "lrset");
+    tag(c->eb, EB_COUNT, "bamenc");
     tag(c->sw.buf, SWB_COUNT, "sw");
     c->n_cu = prop.multiProcessorCount;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
@@ -155,6 +156,7 @@ extern "C" void pr_ctx_destroy(pr_ctx *c) {
     for (auto &b : c->sd) b.release();
     for (auto &b : c->xb) b.release();
     for (auto &b : c->ls) b.release();
+    for (auto &b : c->eb) b.release();
     sw_release(c->sw);
     for (auto &e : c->ev) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);

@@ -68,6 +68,7 @@ static int sw_upload_impl(pr_ctx *c, const pr_sw_batch *b, const pr_seed_task *d
     hipStream_t s = c->stream;
     c->x_ready = c->x_pass = false;   // an exchange of the previous batch must not be consumed
     r.launched = false;
+    ++r.gen;
     int qmax = 1;
     for (int i = 0; i < b->n_sr; ++i) {
         const int64_t l = b->sr_off[i + 1] - b->sr_off[i];
@@ -540,6 +541,7 @@ extern "C" int pr_sw_launch(pr_ctx *c, const pr_sw_opts *o) {
     if (o->a > 15 || o->b > 16) return pr_set_error(PR_ERR_UNSUPPORTED, "match score > 15 or mismatch penalty > 16");
     HIPCHK(hipSetDevice(c->device));
     (void)hipGetLastError();   // a failed earlier call must not poison this one
+    ++r.gen;
     hipStream_t s = c->stream;
     SwOptsDev O;
     O.a = o->a; O.b = o->b; O.o_del = o->o_del; O.e_del = o->e_del; O.o_ins = o->o_ins; O.e_ins = o->e_ins;

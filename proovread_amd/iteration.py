@@ -18,6 +18,11 @@ class IterBatch(C.Structure):
     _fields_ = [("sw", sw.SwBatch), ("task_lr_off", _abi.P64), ("lr_qual", _abi.PU8), ("ref_seq", _abi.PU8)]
 
 
+class BamExportIn(C.Structure):
+    _fields_ = [("lr_first", C.c_int32), ("lr_count", C.c_int32), ("sr_off", _abi.P64), ("sr_names", C.c_void_p),
+                ("sr_name_off", _abi.P64), ("sr_qual", _abi.PU8)]
+
+
 class OwnBatch(C.Structure):
     _fields_ = [("lr0", C.c_int32), ("n_lr", C.c_int32), ("lr_off", _abi.P64), ("ref_seq", _abi.PU8),
                 ("lr_qual", _abi.PU8), ("n_sr", C.c_int32), ("sr_off", _abi.P64), ("sr_seq", _abi.PU8),
@@ -55,6 +60,12 @@ def _setup(L):
     L.pr_srset_sample.argtypes = [C.c_void_p, _abi.P64, C.c_int]
     L.pr_lrset_snapshot.argtypes = [C.c_void_p]
     L.pr_lrset_restore.argtypes = [C.c_void_p]
+    L.pr_iter_export_bam.argtypes = [C.c_void_p, C.POINTER(BamExportIn), C.POINTER(C.c_void_p), _abi.P64, _abi.P64]
+    L.pr_iter_export_bam_bytes.argtypes = [C.c_void_p, C.POINTER(BamExportIn), _abi.P64]
+    L.pr_iter_export_bam_read_bytes.argtypes = [C.c_void_p, C.POINTER(BamExportIn), _abi.P64]
+    L.pr_bam_export_last_ms.argtypes = [C.c_void_p, _abi.PD]
+    L.pr_buffer_free.argtypes = [C.c_void_p]
+    L.pr_buffer_free.restype = None
     L._iter_ready = True
 
 
@@ -185,6 +196,70 @@ class Iteration:
         _abi.check(self.L.pr_iter_handoff_order(self.ctx.h, lr, _abi.ptr(out, C.c_int32), n.value, C.byref(n)),
                    "pr_iter_handoff_order")
         return out[:n.value]
+
+    def _export_in(self, names, name_off, qual, first, n):
+        """pr_bam_export_in for reads [first, first + n) and the arrays it points into."""
+        sr_off = getattr(self, "_sr_off", None)
+        if sr_off is None:
+            sr_off = self._sr_off = np.ascontiguousarray(self.d.sr_off, np.int64)
+        if not (isinstance(names, np.ndarray) and names.dtype == np.uint8 and names.flags.c_contiguous):
+            names = np.frombuffer(bytes(names) + b"\0", np.uint8)
+        name_off = np.ascontiguousarray(name_off, np.int64)
+        if len(name_off) != len(sr_off):
+            raise ValueError("name_off must have one entry per short read of the batch and one more")
+        if qual is not None:
+            if not (isinstance(qual, np.ndarray) and qual.dtype == np.uint8 and qual.flags.c_contiguous):
+                qual = np.frombuffer(bytes(qual) + b"\0", np.uint8)
+            if len(qual) < int(sr_off[-1]):
+                raise ValueError("qual must have the short reads' layout (sr_off)")
+        b = BamExportIn(int(first), int(self.n_lr - first if n is None else n), _abi.ptr(sr_off, C.c_int64),
+                        names.ctypes.data, _abi.ptr(name_off, C.c_int64), _abi.ptr(qual, C.c_uint8))
+        # the library keys its uploads of one launch by the pools' addresses: the arrays of the last
+        # call stay alive here, so no other pool can take their place in memory meanwhile
+        keep, self._exp_keep = getattr(self, "_exp_keep", None), (sr_off, names, name_off, qual)
+        return b, keep
+
+    def export_bam(self, names, name_off, qual=None, first: int = 0, n: Optional[int] = None) -> bytes:
+        """The alignments the last launch handed to the consensus, as BAM records
+        (pr_iter_export_bam): long reads [first, first + n) in order, each read's records in
+        hand-off order -- the body of a coordinate-sorted BAM whose reference ids are the long
+        reads' indices.  names / name_off: the short reads' names as one pool (bytes or a uint8
+        array) with offsets [n_sr + 1], in the batch's order; qual: their phred+33 qualities in
+        the short reads' layout, or None (QUAL absent).  Pass the same arrays for every range of
+        one launch: they are uploaded once."""
+        b, keep = self._export_in(names, name_off, qual, first, n)
+        p, ln, nr = C.c_void_p(), C.c_int64(), C.c_int64()
+        _abi.check(self.L.pr_iter_export_bam(self.ctx.h, C.byref(b), C.byref(p), C.byref(ln), C.byref(nr)),
+                   "pr_iter_export_bam")
+        try:
+            # (a view of the native buffer: ctypes.string_at takes a C int size)
+            out = bytes(memoryview((C.c_ubyte * ln.value).from_address(p.value))) if ln.value else b""
+        finally:
+            self.L.pr_buffer_free(p)
+        self.last_export_records = nr.value
+        return out
+
+    def export_bam_bytes(self, names, name_off, qual=None, first: int = 0, n: Optional[int] = None) -> int:
+        """The size of export_bam's result for the range (pr_iter_export_bam_bytes: the size pass alone)."""
+        b, keep = self._export_in(names, name_off, qual, first, n)
+        ln = C.c_int64()
+        _abi.check(self.L.pr_iter_export_bam_bytes(self.ctx.h, C.byref(b), C.byref(ln)), "pr_iter_export_bam_bytes")
+        return ln.value
+
+    def export_bam_read_bytes(self, names, name_off, qual=None, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """The bytes of each long read's records in the range (pr_iter_export_bam_read_bytes): one
+        size pass gives every cut of a task's ranges."""
+        b, keep = self._export_in(names, name_off, qual, first, n)
+        out = np.zeros(max(1, b.lr_count), np.int64)
+        _abi.check(self.L.pr_iter_export_bam_read_bytes(self.ctx.h, C.byref(b), _abi.ptr(out, C.c_int64)),
+                   "pr_iter_export_bam_read_bytes")
+        return out[:b.lr_count]
+
+    def export_ms(self) -> float:
+        """Kernel time of the last export_bam / export_bam_bytes (HIP events)."""
+        ms = C.c_double()
+        _abi.check(self.L.pr_bam_export_last_ms(self.ctx.h, C.byref(ms)), "pr_bam_export_last_ms")
+        return ms.value
 
     def timing(self):
         v = [C.c_double() for _ in range(4)]
