@@ -770,6 +770,25 @@ int pr_bam_decode_alns_gpu(pr_ctx *ctx, const uint8_t *recs, int64_t len, pr_bam
  * PR_ERR_NOSEQ for a kept record without SEQ (bam2cns:347), PR_ERR_SAM for a bad aux field.   */
 int pr_cns_upload_bam(pr_ctx *ctx, const pr_cns_batch *reads, const uint8_t *recs, int64_t len,
                       const int32_t *ref_to_lr, int32_t n_ref, int64_t *n_kept);
+/* The two calls above with options; flags = 0 is the call without them (the same kernels, the
+ * same refusals).  PR_BAM_RESTORE_SEQ: files of stock mappers (`bwa mem -a`, minimap2: SEQ and
+ * QUAL `*` on FLAG 0x100 records) instead of bwa-proovread's.  What bin/samfilter does to the
+ * mapper's stream before sorting, done by key on the device after it: a kept record without SEQ
+ * takes it from its donor, the lowest-index record of the whole stream (kept or not) with the
+ * same QNAME and FLAG & 0xC0, l_seq > 0, FLAG & 0x904 == 0 and no H op.  With q the record's M + I
+ * + S + = + X lengths and hl / ht its leading / trailing H, hl + q + ht must be the donor's l_seq;
+ * the record gets bases [hl, hl + q) of the donor's SEQ, or of its reverse complement (A<->T,
+ * C<->G, other letters kept: Fasta::Seq->Reverse_complement) when the strands differ, and QUAL
+ * alike (reversed, '!' and PR_ALN_NO_QUAL when the donor has none); PR_ALN_NO_SEQ is cleared.
+ * PR_ERR_NOSEQ without a donor, PR_ERR_SAM for a length mismatch; the message names the QNAME
+ * of the lowest such record.  After a refusal nothing is resident and the context is usable.
+ * n_restored (may be NULL): the columns that took a donor's SEQ.                              */
+#define PR_BAM_RESTORE_SEQ 1u
+int pr_bam_decode_alns_gpu_opts(pr_ctx *ctx, const uint8_t *recs, int64_t len, uint32_t flags, pr_bam_alns *out,
+                                int64_t *n_restored);
+int pr_cns_upload_bam_opts(pr_ctx *ctx, const pr_cns_batch *reads, const uint8_t *recs, int64_t len,
+                           const int32_t *ref_to_lr, int32_t n_ref, uint32_t flags, int64_t *n_kept,
+                           int64_t *n_restored);
 /* pr_cns_bounds_of for the resident batch (pr_cns_upload or pr_cns_upload_bam); its alignments:
  * the count and (aln_off [n_lr + 1], may be NULL) the per-read prefix pr_cns_out.kept follows */
 int pr_cns_resident_bounds(pr_ctx *ctx, pr_cns_bounds *out);

@@ -16,6 +16,7 @@ LIBPATH = Path(os.environ.get("PRGPU_LIB", PKG / "libprgpu.so"))
 PR_ALN_HAS_SCORE = 1
 PR_ALN_NO_QUAL = 2
 PR_ALN_NO_SEQ = 4
+PR_BAM_RESTORE_SEQ = 1
 
 ERRORS = {
     0: "PR_OK", -1: "PR_ERR_ARG", -2: "PR_ERR_HIP", -3: "PR_ERR_SAM", -4: "PR_ERR_NOSEQ",
@@ -91,6 +92,9 @@ def lib():
     # the device BAM decoder (sam / bam modes)
     L.pr_bam_decode_alns_gpu.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p]
     L.pr_cns_upload_bam.argtypes = [C.c_void_p, C.POINTER(CnsBatch), C.c_char_p, C.c_int64, P32, C.c_int32, P64]
+    L.pr_bam_decode_alns_gpu_opts.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_uint32, C.c_void_p, P64]
+    L.pr_cns_upload_bam_opts.argtypes = [C.c_void_p, C.POINTER(CnsBatch), C.c_char_p, C.c_int64, P32, C.c_int32,
+                                         C.c_uint32, P64, P64]
     L.pr_cns_resident_bounds.argtypes = [C.c_void_p, C.POINTER(CnsBounds)]
     L.pr_cns_resident_aln_count.argtypes = [C.c_void_p, P64, P64]
     L.pr_bam_decode_last_ms.argtypes = [C.c_void_p, PD]

@@ -372,26 +372,31 @@ def run_packed(reads: Sequence[LongRead], d: Dict[str, np.ndarray], params: CnsP
 
 
 def run_bam(reads: Sequence[LongRead], bam_path: str, params: CnsParams, ctx: Optional[_abi.Context] = None,
-            raise_on_error: bool = False, split: int = 1, threads: int = 0) -> List[ReadResult]:
+            raise_on_error: bool = False, split: int = 1, threads: int = 0, restore_seq: bool = False) -> List[ReadResult]:
     """The consensus of every read over a coordinate-sorted BAM file (proovread's read-bam task,
     bin/proovread:994-1025 + correct_sr_mt, without the chunk fan-out): the file is inflated on
     host threads, its records are decoded and grouped per read on the device
-    (pr_cns_upload_bam), then one consensus launch.  Results as run_packed's."""
+    (pr_cns_upload_bam), then one consensus launch.  Results as run_packed's.  restore_seq: see
+    run_bam_records."""
     from . import bamio
     with open(bam_path, "rb") as fh:
         stream = bamio._native_inflate(fh.read(), threads)
     h, o = bamio._parse_header(stream)
-    return run_bam_records(reads, [nm for nm, _ in h.refs], stream[o:], params, ctx, raise_on_error, split)
+    return run_bam_records(reads, [nm for nm, _ in h.refs], stream[o:], params, ctx, raise_on_error, split, restore_seq)
 
 
 def run_bam_records(reads: Sequence[LongRead], names: Sequence[str], body: bytes, params: CnsParams,
-                    ctx: Optional[_abi.Context] = None, raise_on_error: bool = False, split: int = 1) -> List[ReadResult]:
+                    ctx: Optional[_abi.Context] = None, raise_on_error: bool = False, split: int = 1,
+                    restore_seq: bool = False) -> List[ReadResult]:
     """run_bam on the reference names of a BAM header and its record stream (block_size-prefixed
     records in coordinate order).  A read takes the records whose reference is named as its id;
     of reads that share an id the first takes them in this pass and the others in a pass of their
     own (pack_bam_chunk gives a repeated id the same records).  split: the reads go in that many
     contiguous ranges, the stream being decoded once per range; a range that does not fit in the
-    device memory (hipMalloc fails) is halved until it does."""
+    device memory (hipMalloc fails) is halved until it does.  restore_seq: a record without SEQ
+    (a stock mapper's FLAG 0x100 lines) takes it from the primary record of its name
+    (PR_BAM_RESTORE_SEQ, include/prgpu.h); every range gets the whole stream, so a donor on a
+    read of another range, or of no range, is found."""
     ctx = ctx or _abi.default_context()
     reads = list(reads)
     first: Dict[str, int] = {}
@@ -410,7 +415,7 @@ def run_bam_records(reads: Sequence[LongRead], names: Sequence[str], body: bytes
         lo, hi = todo.pop(0)
         sub = [reads[main[k]] for k in range(lo, hi)]
         try:
-            res = _run_bam_range(sub, names, body, params, ctx)
+            res = _run_bam_range(sub, names, body, params, ctx, restore_seq)
         except RuntimeError as e:
             if "hipMalloc" not in str(e) or hi - lo < 2:
                 raise
@@ -420,7 +425,8 @@ def run_bam_records(reads: Sequence[LongRead], names: Sequence[str], body: bytes
         for k, r in zip(range(lo, hi), res):
             out[main[k]] = r
     if rest:
-        for i, r in zip(rest, run_bam_records([reads[i] for i in rest], names, body, params, ctx, False, split)):
+        for i, r in zip(rest, run_bam_records([reads[i] for i in rest], names, body, params, ctx, False, split,
+                                            restore_seq)):
             out[i] = r
     if raise_on_error:
         for r in out:
@@ -430,7 +436,7 @@ def run_bam_records(reads: Sequence[LongRead], names: Sequence[str], body: bytes
 
 
 def _run_bam_range(reads: Sequence[LongRead], names: Sequence[str], body: bytes, params: CnsParams,
-                   ctx: _abi.Context) -> List[ReadResult]:
+                   ctx: _abi.Context, restore_seq: bool = False) -> List[ReadResult]:
     """One resident batch: reads with distinct ids, their records from the stream."""
     L = _abi.lib()
     n = len(reads)
@@ -447,8 +453,12 @@ def _run_bam_range(reads: Sequence[LongRead], names: Sequence[str], body: bytes,
     cb.ign_off = P(d.get("ign_off"), C.c_int64)
     cb.ign = P(d.get("ign"), C.c_int32)
     nk = C.c_int64()
-    _abi.check(L.pr_cns_upload_bam(ctx.h, C.byref(cb), body, len(body), P(r2l, C.c_int32) if len(r2l) else None,
-                                   len(r2l), C.byref(nk)), "pr_cns_upload_bam")
+    if restore_seq:
+        _abi.check(L.pr_cns_upload_bam_opts(ctx.h, C.byref(cb), body, len(body), P(r2l, C.c_int32) if len(r2l) else None,
+                                            len(r2l), _abi.PR_BAM_RESTORE_SEQ, C.byref(nk), None), "pr_cns_upload_bam_opts")
+    else:
+        _abi.check(L.pr_cns_upload_bam(ctx.h, C.byref(cb), body, len(body), P(r2l, C.c_int32) if len(r2l) else None,
+                                       len(r2l), C.byref(nk)), "pr_cns_upload_bam")
     _abi.check(L.pr_cns_resident_aln_count(ctx.h, None, P(d["aln_off"], C.c_int64)), "pr_cns_resident_aln_count")
     bd = _abi.CnsBounds()
     _abi.check(L.pr_cns_resident_bounds(ctx.h, C.byref(bd)), "pr_cns_resident_bounds")

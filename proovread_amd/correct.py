@@ -81,6 +81,7 @@ class LoopConfig:
     keep_masked: bool = False              # LoopResult.masked: the last regular task's masked reads
     sam: Optional[str] = None              # --sam: alignments made elsewhere (mode sam, task read-sam)
     bam: Optional[str] = None              # --bam: the same as a coordinate-sorted BAM (mode bam, task read-bam)
+    restore_seq: bool = False              # --restore-secondary-seq: SEQ `*` records take their primary's (read-sam / read-bam)
     keep_temporary: Optional[str] = None   # --keep-temporary-files: the prefix PRE of PRE.<task>.bam / .bam.bai / .fq
 
 
@@ -535,14 +536,16 @@ class GpuStages:
         self.last_export_ms = round(st["ms"], 2)
         return st["records"]
 
-    def external_alignments(self, task: str, path: str, params) -> TaskOut:
+    def external_alignments(self, task: str, path: str, params, restore_seq: bool = False) -> TaskOut:
         """read-sam / read-bam (bin/proovread:718-736): the consensus of every long read over
         alignments made elsewhere, in place of correct_sr_mt's bam2cns chunk fan-out.  read-bam
         takes a coordinate-sorted BAM as it is (the reference runs `samtools index` on it);
         read-sam is `samtools view -bS` + `samtools sort` on the host (pr_sam_encode,
         pr_bam_sort_records, bin/proovread:994-1025 + create_sorted_bam), then the same path.
         The records are decoded and grouped per read on the device (cns.run_bam_records); the
-        consensus replaces the resident reads."""
+        consensus replaces the resident reads.  restore_seq: records without SEQ (a stock mapper's
+        secondary lines) take it from their primary record on the device, in both tasks after
+        the stream is sorted (PR_BAM_RESTORE_SEQ)."""
         from . import _abi, bamio, cns
         cur = self.reads()
         lrs = [cns.LongRead(i, s.decode("latin-1"), q.decode("latin-1")) for i, s, q in zip(cur.ids, cur.seqs, cur.quals)]
@@ -557,7 +560,7 @@ class GpuStages:
                 stream = bamio._native_inflate(fh.read())
             h, o = bamio._parse_header(stream)
             names, body = [nm for nm, _ in h.refs], stream[o:]
-        res = cns.run_bam_records(lrs, names, body, params, ctx=self.ctx)
+        res = cns.run_bam_records(lrs, names, body, params, ctx=self.ctx, restore_seq=restore_seq)
         for r in res:
             if r.status != 0:   # bam2cns exits (Verbose->exit) and proovread stops
                 raise RuntimeError(f"{task}: {r.id}: consensus failed ({_abi.ERRORS.get(r.status, r.status)})")
@@ -729,7 +732,12 @@ def run_tasks(stages, srs: ShortReads, tasks: List[str], cfg: LoopConfig, mode: 
             max_cov = min(cfg.coverage, sr_coverage_for(task)) * cfg.coverage_scale_factor
             params = cns.CnsParams(coverage=max_cov, bin_size=float(T.bin_size(mode)), use_ref_qual=True,
                                    detect_chimera=T.detect_chimera(task), max_ins_length=0)
-            r = stages.external_alignments(task, path, params) if have_reads else TaskOut(0, [])
+            if not have_reads:
+                r = TaskOut(0, [])
+            elif cfg.restore_seq:
+                r = stages.external_alignments(task, path, params, restore_seq=True)
+            else:
+                r = stages.external_alignments(task, path, params)
             ent.n_tasks = r.n_tasks
             chim += r.chim
             if cfg.keep_temporary and have_reads:
@@ -848,6 +856,9 @@ def parse_args(argv: Optional[Sequence[str]] = None):
     ap.add_argument("-s", "--short-reads", action="append", default=[])
     ap.add_argument("--sam", metavar="FILE", help="correct from the alignments of a SAM file (mode sam)")
     ap.add_argument("--bam", metavar="FILE", help="correct from a coordinate-sorted BAM file (mode bam)")
+    ap.add_argument("--restore-secondary-seq", action="store_true",
+                    help="with --sam / --bam: a record without SEQ (`*` on a stock mapper's secondary lines) takes the "
+                         "sequence of the primary record of its name")
     ap.add_argument("-m", "--mode", choices=sorted(T.MODE_TASKS), help="the task list (default: by short-read length)")
     ap.add_argument("-p", "--pre", required=True)
     ap.add_argument("--coverage", type=float, default=50.0)
@@ -863,6 +874,8 @@ def parse_args(argv: Optional[Sequence[str]] = None):
                  "strand bit of FLAG)")
     if not (a.short_reads or a.sam or a.bam):
         ap.error("either -s/--short-reads or --sam / --bam is required")
+    if a.restore_secondary_seq and not (a.sam or a.bam):
+        ap.error("--restore-secondary-seq needs --sam or --bam")
     for opt, f in (("--sam", a.sam), ("--bam", a.bam)):
         if f and not os.path.isfile(f):
             ap.error(f"cannot find {opt[2:].upper()} file `{f}`")
@@ -890,7 +903,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         lrs += list(zip(names, seqs, quals))
     sr_data = b"".join(open(f, "rb").read() for f in a.short_reads)
     cfg = LoopConfig(coverage=a.coverage, sampling=not a.no_sampling, seed_threads=a.threads, mode=a.mode,
-                     sam=a.sam, bam=a.bam, keep_temporary=a.pre if a.keep_temporary_files else None)
+                     sam=a.sam, bam=a.bam, restore_seq=a.restore_secondary_seq, keep_temporary=a.pre if a.keep_temporary_files else None)
     comm, rank = None, 0
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         from . import _abi

@@ -2,6 +2,8 @@
 // decoder alone, downloaded, to compare with pr_bam_decode_alns), pr_cns_upload_bam (a record
 // stream decoded and grouped per long read into the resident consensus batch) and what a driver
 // needs of that batch (pr_cns_resident_bounds, pr_cns_resident_aln_count, pr_bam_decode_last_ms).
+// The two _opts entries take PR_BAM_RESTORE_SEQ: the donor table, the lookup and the restoring
+// unpack run as well, and the host formats a refusal's message from the record index it gets back.
 //
 // The host's share: one pre-pass over the records' sizes (the offsets the kernels index by, and
 // the three size errors of bam_codec.cpp:491-500), the scans over reference ids and long reads
@@ -12,6 +14,7 @@
 // the resident hand-off, the download of the record stream.
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "ctx.h"
@@ -25,7 +28,7 @@ using namespace prgpu::bam;
 namespace {
 
 enum { T_RECS, T_OFF, T_FSCORE, T_FFLAGS, T_FKEEP, T_CNT, T_ERR, T_TEXT, T_KIDX, T_REF2LR, T_REFSTART, T_DELTA,
-       T_SCAN, T_SRC, T_INS, T_COUNT };
+       T_SCAN, T_SRC, T_INS, T_TAB, T_RST, T_SEQSRC, T_HL, T_RC, T_COUNT };
 
 struct Temps {
     DevBuf b[T_COUNT];
@@ -62,15 +65,28 @@ int scan_records(const uint8_t *recs, int64_t len, std::vector<int64_t> &off) {
     return 0;
 }
 
+// the QNAME of record i for a message (at most 64 bytes of it)
+std::string qname_of(const uint8_t *recs, const std::vector<int64_t> &off, unsigned long long i) {
+    const uint8_t *rec = recs + off[(size_t)i];
+    const size_t l = rec[12] ? (size_t)rec[12] - 1 : 0;
+    std::string s((const char *)bam_name_at(rec), l < 64 ? l : 64);
+    if (l > 64) s += "...";
+    return s;
+}
+
 // The passes of bam_kernels.hip over a record stream.  ref_to_lr NULL: every record is kept, in
 // file order; otherwise the kept records come out grouped by long read (n_lr of them).
+// flags & PR_BAM_RESTORE_SEQ: a kept record without SEQ takes it from its donor (bam_core.h);
+// *n_restored counts them.
 int decode(pr_ctx *c, const uint8_t *recs, int64_t len, const int32_t *ref_to_lr, int32_t n_ref, int32_t n_lr,
-           const Columns &O, Decoded &R) {
+           const Columns &O, Decoded &R, uint32_t flags = 0, int64_t *n_restored = nullptr) {
     std::vector<int64_t> off;
     int rc = scan_records(recs, len, off);
     if (rc) return rc;
     const int64_t n = (int64_t)off.size();
     R.n = n;
+    const bool restore = (flags & PR_BAM_RESTORE_SEQ) != 0;
+    if (n_restored) *n_restored = 0;
     std::vector<int32_t> lr_to_ref;
     if (ref_to_lr) {
         lr_to_ref.assign((size_t)n_lr, -1);
@@ -112,6 +128,35 @@ int decode(pr_ctx *c, const uint8_t *recs, int64_t len, const int32_t *ref_to_lr
     D.err = B[T_ERR].as<int32_t>();
     D.text_list = B[T_TEXT].as<int32_t>();
     D.kidx = B[T_KIDX].as<int64_t>();
+    float ms_donor = 0.f;
+    if (restore) {
+        // the donor table: a power of two of slots, at least twice the records that may lend a SEQ
+        // (counted here from the fixed fields; the kernel also leaves out those with an H op)
+        int64_t eligible = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            const uint8_t *rec = recs + off[(size_t)i];
+            eligible += bam_fixed(rec).l_seq > 0 && !(bam_flag(rec) & BAM_DONOR_EXCLUDED);
+        }
+        const int64_t slots = bam_table_slots(eligible);
+        if ((rc = B[T_TAB].ensure((size_t)slots * 8)) || (rc = B[T_RST].ensure(24))) return rc;
+        HIPCHK(hipMemsetAsync(B[T_TAB].p, 0xFF, (size_t)slots * 8, s));
+        HIPCHK(hipMemsetAsync(B[T_RST].p, 0xFF, 16, s));
+        HIPCHK(hipMemsetAsync((uint8_t *)B[T_RST].p + 16, 0, 8, s));
+        D.tab = B[T_TAB].as<unsigned long long>();
+        D.tab_mask = slots - 1;
+        D.rst = B[T_RST].as<unsigned long long>();
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        HIPCHK(hipEventCreate(&e0));
+        hipError_t he = hipEventCreate(&e1);
+        if (he == hipSuccess) he = hipEventRecord(e0, s);
+        if (he == hipSuccess) he = (hipError_t)bam_donor_pass(D, s);
+        if (he == hipSuccess) he = hipEventRecord(e1, s);
+        if (he == hipSuccess) he = hipEventSynchronize(e1);
+        if (he == hipSuccess) (void)hipEventElapsedTime(&ms_donor, e0, e1);
+        (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        HIPCHK(he);
+    }
 
     // field pass + the kept records' indices
     HIPCHK(hipEventRecord(T.ev[0], s));
@@ -154,6 +199,12 @@ int decode(pr_ctx *c, const uint8_t *recs, int64_t len, const int32_t *ref_to_lr
         (rc = O.flags->ensure(k1)) || (rc = O.seq_off->ensure(k1 * 8)) || (rc = O.lseq->ensure(k1 * 4)) ||
         (rc = O.cig_off->ensure(k1 * 8)) || (rc = O.ncig->ensure(k1 * 4)) || (rc = B[T_SRC].ensure(k1 * 8)))
         return rc;
+    if (restore) {
+        if ((rc = B[T_SEQSRC].ensure(k1 * 8)) || (rc = B[T_HL].ensure(k1 * 4)) || (rc = B[T_RC].ensure(k1))) return rc;
+        D.a_seq_src = B[T_SEQSRC].as<int64_t>();
+        D.a_hl = B[T_HL].as<int32_t>();
+        D.a_rc = B[T_RC].as<uint8_t>();
+    }
     HIPCHK(hipMemsetAsync(O.lseq->p, 0, k1 * 4, s));
     HIPCHK(hipMemsetAsync(O.ncig->p, 0, k1 * 4, s));
     HIPCHK(hipMemsetAsync(B[T_SRC].p, 0, k1 * 8, s));
@@ -168,14 +219,31 @@ int decode(pr_ctx *c, const uint8_t *recs, int64_t len, const int32_t *ref_to_lr
     D.seq_off = O.seq_off->as<int64_t>();
     D.cig_off = O.cig_off->as<int64_t>();
     HIPCHK(hipEventRecord(T.ev[2], s));
-    HIPCHK((hipError_t)bam_place_pass(D, O.seq_off->as<int64_t>(), O.cig_off->as<int64_t>(), B[T_SCAN].p, tb, s));
+    if (restore)
+        HIPCHK((hipError_t)bam_place_restore_pass(D, O.seq_off->as<int64_t>(), O.cig_off->as<int64_t>(), B[T_SCAN].p, tb, s));
+    else
+        HIPCHK((hipError_t)bam_place_pass(D, O.seq_off->as<int64_t>(), O.cig_off->as<int64_t>(), B[T_SCAN].p, tb, s));
     HIPCHK(hipEventRecord(T.ev[3], s));
     HIPCHK(hipMemcpyAsync(err, B[T_ERR].p, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(&R.seq_len, O.seq_off->as<int64_t>() + n_kept, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(&R.cig_len, O.cig_off->as<int64_t>() + n_kept, 8, hipMemcpyDeviceToHost, s));
+    unsigned long long rst[3] = {0, 0, 0};
+    if (restore) HIPCHK(hipMemcpyAsync(rst, B[T_RST].p, 24, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (err[0] & BAM_E_ORDER) return pr_set_error(PR_ERR_ARG, "BAM records are not coordinate-sorted");
-    if (err[0] & BAM_E_NOSEQ) return pr_set_error(PR_ERR_NOSEQ, "Cannot handle BAM secondary alignments without seq/qual");
+    if (restore) {
+        // (the placement's BAM_E_NOSEQ is what the lookup answers; the lower record index speaks first)
+        const bool nd = (err[0] & BAM_E_NODONOR) != 0, dl = (err[0] & BAM_E_DONORLEN) != 0;
+        if (nd && (!dl || rst[0] < rst[1]))
+            return set_error(PR_ERR_NOSEQ, "Cannot restore SEQ of BAM record %llu (%s): no primary record with SEQ and "
+                             "without hard clips under its name", rst[0], qname_of(recs, off, rst[0]).c_str());
+        if (dl)
+            return set_error(PR_ERR_SAM, "Cannot restore SEQ of BAM record %llu (%s): its CIGAR does not span its "
+                             "primary record's SEQ", rst[1], qname_of(recs, off, rst[1]).c_str());
+        if (n_restored) *n_restored = (int64_t)rst[2];
+    } else if (err[0] & BAM_E_NOSEQ) {
+        return pr_set_error(PR_ERR_NOSEQ, "Cannot handle BAM secondary alignments without seq/qual");
+    }
 
     // SEQ, QUAL and CIGAR ops into the pools
     if ((rc = O.seq->ensure((size_t)R.seq_len + 16)) || (O.qual && (rc = O.qual->ensure((size_t)R.seq_len + 16))) ||
@@ -185,7 +253,7 @@ int decode(pr_ctx *c, const uint8_t *recs, int64_t len, const int32_t *ref_to_lr
     D.qual = O.qual ? O.qual->as<uint8_t>() : nullptr;
     D.cig = O.cig->as<uint32_t>();
     HIPCHK(hipEventRecord(T.ev[4], s));
-    HIPCHK((hipError_t)bam_unpack_pass(D, s));
+    HIPCHK((hipError_t)(restore ? bam_unpack_restore_pass(D, s) : bam_unpack_pass(D, s)));
     HIPCHK(hipEventRecord(T.ev[5], s));
 
     // AS:Z / AS:H scores: Perl's number of the text, into the score column
@@ -219,7 +287,7 @@ int decode(pr_ctx *c, const uint8_t *recs, int64_t len, const int32_t *ref_to_lr
     }
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
-    c->ms_bam = 0.f;
+    c->ms_bam = ms_donor;
     for (int k = 0; k < 6; k += 2) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, T.ev[k], T.ev[k + 1]) == hipSuccess) c->ms_bam += ms;
@@ -230,7 +298,13 @@ int decode(pr_ctx *c, const uint8_t *recs, int64_t len, const int32_t *ref_to_lr
 }   // namespace
 
 extern "C" int pr_bam_decode_alns_gpu(pr_ctx *c, const uint8_t *recs, int64_t len, pr_bam_alns *out) {
+    return pr_bam_decode_alns_gpu_opts(c, recs, len, 0, out, nullptr);
+}
+
+extern "C" int pr_bam_decode_alns_gpu_opts(pr_ctx *c, const uint8_t *recs, int64_t len, uint32_t flags, pr_bam_alns *out,
+                                           int64_t *n_restored) {
     if (!c || !out || len < 0 || (len && !recs)) return pr_set_error(PR_ERR_ARG, "null arg");
+    if (flags & ~(uint32_t)PR_BAM_RESTORE_SEQ) return set_error(PR_ERR_ARG, "unknown BAM decode flags 0x%x", flags);
     std::memset(out, 0, sizeof *out);
     struct Bufs {
         DevBuf b[11];
@@ -242,7 +316,7 @@ extern "C" int pr_bam_decode_alns_gpu(pr_ctx *c, const uint8_t *recs, int64_t le
     DevBuf *b = U.b;
     const Columns O = {&b[0], &b[1], &b[2], &b[3], &b[4], &b[5], &b[6], &b[7], &b[8], &b[9], &b[10]};
     Decoded R;
-    int rc = decode(c, recs, len, nullptr, 0, 0, O, R);
+    int rc = decode(c, recs, len, nullptr, 0, 0, O, R, flags, n_restored);
     if (rc) return rc;
     const size_t n = (size_t)R.n_kept;
     auto alloc = [](size_t bytes) { return std::malloc(bytes ? bytes : 1); };
@@ -281,8 +355,15 @@ extern "C" int pr_bam_decode_alns_gpu(pr_ctx *c, const uint8_t *recs, int64_t le
 
 extern "C" int pr_cns_upload_bam(pr_ctx *c, const pr_cns_batch *reads, const uint8_t *recs, int64_t len,
                                  const int32_t *ref_to_lr, int32_t n_ref, int64_t *n_kept) {
+    return pr_cns_upload_bam_opts(c, reads, recs, len, ref_to_lr, n_ref, 0, n_kept, nullptr);
+}
+
+extern "C" int pr_cns_upload_bam_opts(pr_ctx *c, const pr_cns_batch *reads, const uint8_t *recs, int64_t len,
+                                      const int32_t *ref_to_lr, int32_t n_ref, uint32_t flags, int64_t *n_kept,
+                                      int64_t *n_restored) {
     if (!c || !reads || len < 0 || (len && !recs) || n_ref < 0 || (n_ref && !ref_to_lr))
         return pr_set_error(PR_ERR_ARG, "null arg");
+    if (flags & ~(uint32_t)PR_BAM_RESTORE_SEQ) return set_error(PR_ERR_ARG, "unknown BAM decode flags 0x%x", flags);
     const int32_t n = reads->n_lr;
     if (n < 0 || (n && !reads->lr_off)) return pr_set_error(PR_ERR_ARG, "lr_off required");
     if (n && reads->lr_off[0] != 0) return pr_set_error(PR_ERR_ARG, "offsets must start at 0");
@@ -297,7 +378,7 @@ extern "C" int pr_cns_upload_bam(pr_ctx *c, const pr_cns_batch *reads, const uin
     const Columns O = {nullptr, &B[CB_POS], &B[CB_SCORE], &B[CB_AFLAGS], &B[CB_SEQ_OFF], &B[CB_LSEQ], &B[CB_CIG_OFF],
                        &B[CB_NCIG], &B[CB_SEQ], nullptr, &B[CB_CIG]};
     Decoded R;
-    if ((rc = decode(c, recs, len, n_ref ? ref_to_lr : &none, n_ref ? n_ref : 1, n, O, R))) return rc;
+    if ((rc = decode(c, recs, len, n_ref ? ref_to_lr : &none, n_ref ? n_ref : 1, n, O, R, flags, n_restored))) return rc;
     // offsets, output bounds and the byte model as pr_cns_upload derives them from a host batch
     c->n_aln = R.n_kept;
     c->aln_off_host.assign((size_t)n + 1, 0);

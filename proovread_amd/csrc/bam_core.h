@@ -9,6 +9,10 @@
 // one aligned 16-byte store, the partial chunks at the two ends of a record are byte stores.  The
 // unpack functions take (lane, nlanes): lane l handles chunks l, l + nlanes, ..; the kernels
 // call them with a 16-lane group per record, the host with nlanes = 1 or lane by lane.
+//
+// The second half of the file is PR_BAM_RESTORE_SEQ's: the key of a record, the donor table, the
+// CIGAR walk and the unpack of a slice of another record's SEQ / QUAL in either orientation
+// (host build: tests/native/bam_restore_host.cpp).
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -239,6 +243,219 @@ BAM_HD int64_t bam_copy_cigar(const uint8_t *c, int32_t n, uint32_t *dst, int la
         if ((op & 15u) == 1u) ins += op >> 4;
     }
     return ins;
+}
+
+// ---------------------------------------------------------------------------------------------
+// SEQ of records that have none (PR_BAM_RESTORE_SEQ; stock `bwa mem -a` and minimap2 print `*` on
+// FLAG 0x100 records).  The rule, for a kept record r with l_seq == 0:
+//   1. key    the QNAME bytes plus FLAG & 0xC0 (first / second mate).
+//   2. donor  the record of the whole stream (kept or not, on any reference) with the same key,
+//             l_seq > 0, FLAG & 0x904 == 0 (not secondary, supplementary or unmapped) and no H op
+//             in its CIGAR; of several the lowest record index.  None: PR_ERR_NOSEQ.
+//   3. length q = the sum of r's M, I, S, =, X lengths, hl / ht = the length of a leading /
+//             trailing H op of r (a lone H op is the leading one).  hl + q + ht must be the
+//             donor's l_seq, else PR_ERR_SAM.
+//   4. o      the donor's SEQ when (r.FLAG ^ donor.FLAG) & 0x10 == 0; otherwise reversed with
+//             A<->T and C<->G exchanged and every other letter kept (Fasta::Seq's
+//             Reverse_complement: no IUPAC complement).  QUAL is reversed alike.
+//   5. result r's SEQ is o[hl : hl + q], QUAL the same slice ('!' fill and PR_ALN_NO_QUAL when
+//             the donor has none); the column's l_seq is q and PR_ALN_NO_SEQ is cleared.
+enum { BAM_DONOR_EXCLUDED = 0x904, BAM_MATE_BITS = 0xC0, BAM_REVERSE = 0x10 };
+
+BAM_HD uint32_t bam_flag(const uint8_t *rec) { return bam_rd16(rec + 18); }
+BAM_HD const uint8_t *bam_name_at(const uint8_t *rec) { return rec + 36; }
+
+// FNV-1a over the name bytes (the NUL included) and the mate bits, then a 64-bit finalizer
+BAM_HD uint64_t bam_key_hash(const uint8_t *rec, const Fixed &f) {
+    uint64_t h = 0xcbf29ce484222325ull;
+    const uint8_t *nm = bam_name_at(rec);
+    for (int32_t k = 0; k < f.l_read_name; ++k) h = (h ^ nm[k]) * 0x100000001b3ull;
+    h = (h ^ (bam_flag(rec) & BAM_MATE_BITS)) * 0x100000001b3ull;
+    h ^= h >> 33;
+    h *= 0xff51afd7ed558ccdull;
+    h ^= h >> 33;
+    return h;
+}
+
+// the same key: name length, name bytes, mate bits
+BAM_HD bool bam_key_equal(const uint8_t *a, const Fixed &fa, const uint8_t *b, const Fixed &fb) {
+    if (fa.l_read_name != fb.l_read_name || ((bam_flag(a) ^ bam_flag(b)) & BAM_MATE_BITS)) return false;
+    const uint8_t *na = bam_name_at(a), *nb = bam_name_at(b);
+    for (int32_t k = 0; k < fa.l_read_name; ++k)
+        if (na[k] != nb[k]) return false;
+    return true;
+}
+
+struct CigarSpan {
+    int64_t q;         // M, I, S, =, X lengths
+    int64_t hl, ht;    // leading / trailing H
+    bool has_h;        // an H op anywhere
+};
+
+BAM_HD CigarSpan bam_cigar_span(const uint8_t *rec, const Fixed &f) {
+    CigarSpan s;
+    s.q = s.hl = s.ht = 0;
+    s.has_h = false;
+    const uint8_t *c = bam_cigar_at(rec, f);
+    for (int32_t j = 0; j < f.n_cigar; ++j) {
+        const uint32_t op = bam_rd32(c + 4 * (int64_t)j), t = op & 15u;
+        const int64_t l = op >> 4;
+        if (t == 0u || t == 1u || t == 4u || t == 7u || t == 8u) s.q += l;
+        if (t == 5u) {
+            s.has_h = true;
+            if (j == 0) s.hl = l;
+            else if (j == f.n_cigar - 1) s.ht = l;
+        }
+    }
+    return s;
+}
+
+// a record that may lend its SEQ
+BAM_HD bool bam_is_donor(const uint8_t *rec, const Fixed &f) {
+    return f.l_seq > 0 && !(bam_flag(rec) & BAM_DONOR_EXCLUDED) && !bam_cigar_span(rec, f).has_h;
+}
+
+// the 4-bit codes of bases first .. first + 15 (all inside the SEQ), base j at bits 4 j, from the
+// 8 or 9 bytes that hold them
+BAM_HD uint64_t bam_codes16(const uint8_t *sb, int32_t first) {
+    const uint8_t *p = sb + (first >> 1);
+    uint64_t v = 0;
+    if (first & 1) {
+        uint32_t prev = p[0];
+        for (int j = 0; j < 8; ++j) {
+            const uint32_t b = p[j + 1];
+            v |= (uint64_t)((prev & 15u) | (b & 0xf0u)) << (8 * j);
+            prev = b;
+        }
+    } else {
+        for (int j = 0; j < 8; ++j) {
+            const uint32_t b = p[j];
+            v |= (uint64_t)(((b >> 4) & 15u) | ((b & 15u) << 4)) << (8 * j);
+        }
+    }
+    return v;
+}
+
+// A<->T (1, 8), C<->G (2, 4), every other code itself
+BAM_HD uint32_t bam_code_complement(uint32_t x) { return (uint32_t)(0xFEDCBA9176523480ull >> (4 * x)) & 15u; }
+
+// sixteen 4-bit codes in the opposite order
+BAM_HD uint64_t bam_reverse_codes(uint64_t v) {
+    v = ((v & 0x00000000ffffffffull) << 32) | (v >> 32);
+    v = ((v & 0x0000ffff0000ffffull) << 16) | ((v >> 16) & 0x0000ffff0000ffffull);
+    v = ((v & 0x00ff00ff00ff00ffull) << 8) | ((v >> 8) & 0x00ff00ff00ff00ffull);
+    return ((v & 0x0f0f0f0f0f0f0f0full) << 4) | ((v >> 4) & 0x0f0f0f0f0f0f0f0full);
+}
+
+// base k of the slice [start, start + n) of a donor's SEQ of dl bases in the record's orientation
+BAM_HD uint32_t bam_base_from(const uint8_t *sb, int32_t dl, int32_t start, bool rev, int32_t k) {
+    const int32_t s = rev ? dl - 1 - (start + k) : start + k;
+    const uint32_t x = (sb[s >> 1] >> (4 * (1 - (s & 1)))) & 15u;
+    return bam_nt16_char(rev ? bam_code_complement(x) : x);
+}
+
+// SEQ from a donor: n bases o[start : start + n) at dst, o = the donor's dl bases at sb or (rev)
+// their reverse complement; start + n <= dl.  The chunks are those of bam_unpack_seq.
+BAM_HD void bam_unpack_seq_from(const uint8_t *sb, int32_t dl, int32_t start, int32_t n, bool rev, uint8_t *dst, int lane,
+                                int nlanes) {
+    const int32_t a0 = bam_line_offset(dst), nc = bam_chunks(a0, n);
+    for (int32_t c = lane; c < nc; c += nlanes) {
+        const int32_t k0 = 16 * c - a0;
+        if (k0 >= 0 && k0 + 16 <= n) {
+            // forward: bases start + k0 ..; reverse: bases dl - 1 - (start + k0) downwards
+            const uint64_t v = rev ? bam_reverse_codes(bam_codes16(sb, dl - 16 - (start + k0))) : bam_codes16(sb, start + k0);
+            Chunk o;
+            for (int w = 0; w < 4; ++w) {
+                uint32_t x = 0;
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t code = (uint32_t)(v >> (4 * (4 * w + j))) & 15u;
+                    x |= bam_nt16_char(rev ? bam_code_complement(code) : code) << (8 * j);
+                }
+                o.w[w] = x;
+            }
+            bam_store_chunk(dst + k0, o);
+        } else {
+            const int32_t lo = k0 < 0 ? 0 : k0, hi = k0 + 16 < n ? k0 + 16 : n;
+            for (int32_t k = lo; k < hi; ++k) dst[k] = (uint8_t)bam_base_from(sb, dl, start, rev, k);
+        }
+    }
+}
+
+// QUAL from a donor, the same slice and orientation (never complemented); '!' x n when absent
+BAM_HD void bam_unpack_qual_from(const uint8_t *qb, int32_t dl, int32_t start, int32_t n, bool rev, bool no_qual,
+                                 uint8_t *dst, int lane, int nlanes) {
+    const int32_t a0 = bam_line_offset(dst), nc = bam_chunks(a0, n);
+    for (int32_t c = lane; c < nc; c += nlanes) {
+        const int32_t k0 = 16 * c - a0;
+        if (k0 >= 0 && k0 + 16 <= n) {
+            Chunk o;
+            for (int w = 0; w < 4; ++w) {
+                uint32_t q = 0u;
+                if (!no_qual) {
+                    if (rev) {
+                        const uint8_t *p = qb + (dl - 1 - (start + k0 + 4 * w));   // the word's first byte, read downwards
+                        q = (uint32_t)p[0] | ((uint32_t)p[-1] << 8) | ((uint32_t)p[-2] << 16) | ((uint32_t)p[-3] << 24);
+                    } else {
+                        q = bam_rd32(qb + start + k0 + 4 * w);
+                    }
+                }
+                o.w[w] = ((q & 0x7f7f7f7fu) + 0x21212121u) ^ (q & 0x80808080u);
+            }
+            bam_store_chunk(dst + k0, o);
+        } else {
+            const int32_t lo = k0 < 0 ? 0 : k0, hi = k0 + 16 < n ? k0 + 16 : n;
+            for (int32_t k = lo; k < hi; ++k)
+                dst[k] = no_qual ? (uint8_t)'!' : (uint8_t)(qb[rev ? dl - 1 - (start + k) : start + k] + 33);
+        }
+    }
+}
+
+// The donor table: open addressing with linear probing over record indices, BAM_SLOT_EMPTY where
+// free; a power of two of slots, at least twice the donors, so a probe always ends.
+static const unsigned long long BAM_SLOT_EMPTY = ~0ull;
+
+BAM_HD int64_t bam_table_slots(int64_t eligible) {
+    int64_t cap = 16;
+    while (cap < 2 * eligible) cap <<= 1;
+    return cap;
+}
+
+// Donor record i (at r) into the table.  A free slot is claimed by a 64-bit compare-and-swap on
+// the index; an occupant of the same key keeps the lower index (a minimum: the slot's key never
+// changes); any other occupant, a hash collision included, costs one more probe.  On the device
+// many lanes insert at once; a host build inserts one record after the other.
+BAM_HD void bam_table_insert(unsigned long long *tab, int64_t mask, const uint8_t *recs, const int64_t *off, int64_t i,
+                             const uint8_t *r, const Fixed &fr) {
+    for (int64_t h = (int64_t)(bam_key_hash(r, fr) & (uint64_t)mask), step = 0; step <= mask; h = (h + 1) & mask, ++step) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        const unsigned long long v = atomicCAS(tab + h, BAM_SLOT_EMPTY, (unsigned long long)i);
+#else
+        const unsigned long long v = tab[h];
+        if (v == BAM_SLOT_EMPTY) tab[h] = (unsigned long long)i;
+#endif
+        if (v == BAM_SLOT_EMPTY) return;
+        const uint8_t *o = recs + off[v];
+        if (bam_key_equal(o, bam_fixed(o), r, fr)) {
+#if defined(__HIP_DEVICE_COMPILE__)
+            atomicMin(tab + h, (unsigned long long)i);
+#else
+            if ((unsigned long long)i < tab[h]) tab[h] = (unsigned long long)i;
+#endif
+            return;
+        }
+    }
+}
+
+// The donor of record r in a filled table (its key hashed and compared by full name), or -1
+BAM_HD int64_t bam_table_find(const unsigned long long *tab, int64_t mask, const uint8_t *recs, const int64_t *off,
+                              const uint8_t *r, const Fixed &fr) {
+    for (int64_t h = (int64_t)(bam_key_hash(r, fr) & (uint64_t)mask), step = 0; step <= mask; h = (h + 1) & mask, ++step) {
+        const unsigned long long v = tab[h];
+        if (v == BAM_SLOT_EMPTY) return -1;
+        const uint8_t *o = recs + off[v];
+        if (bam_key_equal(o, bam_fixed(o), r, fr)) return (int64_t)v;
+    }
+    return -1;
 }
 
 }   // namespace bam

@@ -6,7 +6,8 @@
 namespace prgpu {
 
 // error bits of BamDev.err[0]
-enum { BAM_E_AUX = 1, BAM_E_RID = 2, BAM_E_ORDER = 4, BAM_E_NOSEQ = 8 };
+enum { BAM_E_AUX = 1, BAM_E_RID = 2, BAM_E_ORDER = 4, BAM_E_NOSEQ = 8,
+       BAM_E_NODONOR = 16, BAM_E_DONORLEN = 32 };   // PR_BAM_RESTORE_SEQ only (bam_core.h states the rule)
 
 struct BamDev {
     const uint8_t *recs;         // the record stream (block_size-prefixed records)
@@ -37,6 +38,14 @@ struct BamDev {
     uint8_t *seq, *qual;         // pools (qual may be NULL)
     uint32_t *cig;
     unsigned long long *ins;     // [n_lr] inserted bases of a long read's alignments (zeroed by the caller), or NULL
+    // PR_BAM_RESTORE_SEQ (all NULL / 0 without it: the three kernels above never read them)
+    unsigned long long *tab;     // [tab_mask + 1] the donor table: record indices, BAM_SLOT_EMPTY where free
+    int64_t tab_mask;
+    unsigned long long *rst;     // [0] lowest record without a donor, [1] lowest record whose lengths differ from
+                                 // its donor's (both ~0 from the caller), [2] restored columns (zeroed)
+    int64_t *a_seq_src;          // [n_kept] the record whose SEQ / QUAL a column takes (its own, or the donor)
+    int32_t *a_hl;               // [n_kept] first base of the slice in the record's orientation (the leading H)
+    uint8_t *a_rc;               // [n_kept] 1: the donor lies on the other strand
 };
 
 size_t bam_scan_temp_bytes(int64_t n);
@@ -44,5 +53,11 @@ size_t bam_scan_temp_bytes(int64_t n);
 int bam_field_pass(const BamDev &D, int64_t *kidx_out, void *temp, size_t temp_bytes, void *stream);
 int bam_place_pass(const BamDev &D, int64_t *seq_off_out, int64_t *cig_off_out, void *temp, size_t temp_bytes, void *stream);
 int bam_unpack_pass(const BamDev &D, void *stream);
+// PR_BAM_RESTORE_SEQ: the donor table of the stream; bam_place_pass with the lookup of every
+// column without SEQ between the placement and the scans; bam_unpack_pass reading SEQ / QUAL
+// through a_seq_src
+int bam_donor_pass(const BamDev &D, void *stream);
+int bam_place_restore_pass(const BamDev &D, int64_t *seq_off_out, int64_t *cig_off_out, void *temp, size_t temp_bytes, void *stream);
+int bam_unpack_restore_pass(const BamDev &D, void *stream);
 
 }   // namespace prgpu

@@ -17,6 +17,17 @@
 //                       CIGAR ops into the pools, each lane writing aligned 16-byte chunks; the
 //                       inserted bases of a long read's CIGARs are summed for the output bound.
 // The passes are bandwidth-bound streaming; records are read bytewise (unaligned fields).
+//
+// With PR_BAM_RESTORE_SEQ (bam_core.h states the rule) three more kernels run, and the unpack
+// kernel above is replaced by its twin; without it none of them is launched:
+//   bam_donor_kernel    one lane per record of the whole stream: a record that may lend its SEQ
+//                       goes into the donor table (open addressing in HBM, bam_table_insert).
+//   bam_lookup_kernel   after the placement, one lane per column: a column without SEQ probes
+//                       the table by its record's key, checks the lengths against its CIGAR and
+//                       writes a_seq_src / a_hl / a_rc and a_lseq = q before the seq_off scan.  A
+//                       missing donor or a length mismatch sets an error bit and leaves the lowest
+//                       such record index (atomicMin) for the host's message.
+//   bam_unpack_restore_kernel   bam_unpack_kernel with SEQ / QUAL read through a_seq_src.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
 
@@ -116,6 +127,86 @@ __global__ __launch_bounds__(256) void bam_unpack_kernel(BamDev D) {
     }
 }
 
+__global__ __launch_bounds__(256) void bam_donor_kernel(BamDev D) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < D.n; i += (int64_t)gridDim.x * 256) {
+        const uint8_t *rec = D.recs + D.off[i];
+        const Fixed f = bam_fixed(rec);
+        if (bam_is_donor(rec, f)) bam_table_insert(D.tab, D.tab_mask, D.recs, D.off, i, rec, f);
+    }
+}
+
+__global__ __launch_bounds__(256) void bam_lookup_kernel(BamDev D) {
+    for (int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x; d < D.n_kept; d += (int64_t)gridDim.x * 256) {
+        const int64_t i = D.a_src[d];
+        int64_t src = i;
+        int32_t hl = 0;
+        uint8_t rc = 0;
+        bool restored = false;
+        if (D.a_flags[d] & PR_ALN_NO_SEQ) {
+            const uint8_t *rec = D.recs + D.off[i];
+            const Fixed f = bam_fixed(rec);
+            const int64_t dn = bam_table_find(D.tab, D.tab_mask, D.recs, D.off, rec, f);
+            if (dn < 0) {
+                atomicOr(D.err, BAM_E_NODONOR);
+                atomicMin(D.rst + 0, (unsigned long long)i);
+            } else {
+                const uint8_t *drec = D.recs + D.off[dn];
+                const Fixed df = bam_fixed(drec);
+                const CigarSpan sp = bam_cigar_span(rec, f);
+                if (sp.hl + sp.q + sp.ht != (int64_t)df.l_seq) {
+                    atomicOr(D.err, BAM_E_DONORLEN);
+                    atomicMin(D.rst + 1, (unsigned long long)i);
+                } else {
+                    src = dn;
+                    hl = (int32_t)sp.hl;
+                    rc = ((bam_flag(rec) ^ bam_flag(drec)) & BAM_REVERSE) ? 1 : 0;
+                    D.a_lseq[d] = (int32_t)sp.q;
+                    D.a_flags[d] = (uint8_t)((D.a_flags[d] & ~PR_ALN_NO_SEQ) | bam_seq_flags(drec, df));
+                    restored = true;
+                }
+            }
+        }
+        D.a_seq_src[d] = src;
+        D.a_hl[d] = hl;
+        D.a_rc[d] = rc;
+        // the wave's restored columns: one add
+        const unsigned long long m = __ballot(restored);
+        if (restored && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1)) atomicAdd(D.rst + 2, (unsigned long long)__popcll(m));
+    }
+}
+
+__global__ __launch_bounds__(256) void bam_unpack_restore_kernel(BamDev D) {
+    const int lane = threadIdx.x & 15;
+    for (int64_t d = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4; d < D.n_kept; d += (int64_t)gridDim.x * 16) {
+        const int64_t i = D.a_src[d], si = D.a_seq_src[d];
+        const uint8_t *rec = D.recs + D.off[i];
+        const Fixed f = bam_fixed(rec);
+        const int64_t so = D.seq_off[d];
+        if (si == i) {
+            bam_unpack_seq(bam_seq_at(rec, f), f.l_seq, D.seq + so, lane, 16);
+            if (D.qual) {
+                const uint8_t *qb = bam_qual_at(rec, f);
+                bam_unpack_qual(qb, f.l_seq, f.l_seq > 0 && qb[0] == 0xFF, D.qual + so, lane, 16);
+            }
+        } else {
+            const uint8_t *drec = D.recs + D.off[si];
+            const Fixed df = bam_fixed(drec);
+            const int32_t q = D.a_lseq[d], hl = D.a_hl[d];
+            const bool rc = D.a_rc[d] != 0;
+            bam_unpack_seq_from(bam_seq_at(drec, df), df.l_seq, hl, q, rc, D.seq + so, lane, 16);
+            if (D.qual) {
+                const uint8_t *qb = bam_qual_at(drec, df);
+                bam_unpack_qual_from(qb, df.l_seq, hl, q, rc, qb[0] == 0xFF, D.qual + so, lane, 16);
+            }
+        }
+        long long ins = bam_copy_cigar(bam_cigar_at(rec, f), f.n_cigar, D.cig + D.cig_off[d], lane, 16);
+        if (D.ins) {
+            for (int m = 8; m; m >>= 1) ins += __shfl_xor(ins, m, 16);
+            if (lane == 0 && ins) atomicAdd(D.ins + D.ref_to_lr[f.rid], (unsigned long long)ins);
+        }
+    }
+}
+
 unsigned grid_for(int64_t items) {
     int64_t b = (items + 255) / 256;
     return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
@@ -151,6 +242,36 @@ int bam_place_pass(const BamDev &D, int64_t *seq_off_out, int64_t *cig_off_out, 
     tb = temp_bytes;
     return (int)rocprim::exclusive_scan(temp, tb, D.a_ncig, cig_off_out, (int64_t)0, (size_t)(D.n_kept + 1),
                                         rocprim::plus<int64_t>(), s);
+}
+
+int bam_donor_pass(const BamDev &D, void *stream) {
+    if (D.n <= 0) return 0;
+    hipLaunchKernelGGL(bam_donor_kernel, dim3(grid_for(D.n)), dim3(256), 0, (hipStream_t)stream, D);
+    return (int)hipGetLastError();
+}
+
+int bam_place_restore_pass(const BamDev &D, int64_t *seq_off_out, int64_t *cig_off_out, void *temp, size_t temp_bytes, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(bam_place_kernel, dim3(grid_for(D.n)), dim3(256), 0, s, D);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    if (D.n_kept > 0) {
+        hipLaunchKernelGGL(bam_lookup_kernel, dim3(grid_for(D.n_kept)), dim3(256), 0, s, D);
+        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    }
+    size_t tb = temp_bytes;
+    if ((e = rocprim::exclusive_scan(temp, tb, D.a_lseq, seq_off_out, (int64_t)0, (size_t)(D.n_kept + 1),
+                                     rocprim::plus<int64_t>(), s)) != hipSuccess)
+        return (int)e;
+    tb = temp_bytes;
+    return (int)rocprim::exclusive_scan(temp, tb, D.a_ncig, cig_off_out, (int64_t)0, (size_t)(D.n_kept + 1),
+                                        rocprim::plus<int64_t>(), s);
+}
+
+int bam_unpack_restore_pass(const BamDev &D, void *stream) {
+    if (D.n_kept <= 0) return 0;
+    hipLaunchKernelGGL(bam_unpack_restore_kernel, dim3(grid_for(D.n_kept * 16)), dim3(256), 0, (hipStream_t)stream, D);
+    return (int)hipGetLastError();
 }
 
 int bam_unpack_pass(const BamDev &D, void *stream) {

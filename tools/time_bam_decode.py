@@ -10,6 +10,13 @@ One warm-up, then the median of REPEATS runs each.  The kernels' share of the HB
 (bytes read + bytes written) / kernel time over 8 TB/s, with the byte count written out below.
 
     python tools/time_bam_decode.py [out.json]
+
+--restore times PR_BAM_RESTORE_SEQ instead: every third secondary line of the
+mapping loses its SEQ and QUAL (`*`), a third of all records.  (on) pr_cns_upload_bam_opts with
+the option on that stream; (off) pr_cns_upload_bam on the mapping as it is, whose secondary lines
+carry what the option restores.  Both decode kernel times are pr_bam_decode_last_ms.
+
+    python tools/time_bam_decode.py --restore [out.json]
 """
 import ctypes as C
 import io
@@ -38,9 +45,81 @@ def median_ms(fn):
     return round(statistics.median(t), 3), [round(x, 3) for x in t]
 
 
+def strip_secondaries(sam_text: str):
+    """(lines with `*` on every third secondary line, the lines as mapped).  The drop-in prints
+    the read's SEQ / QUAL on its secondary lines, in the line's orientation and without hard
+    clips: what the option restores from the primary line, so the mapping itself is the restored
+    stream.  About twenty of twenty-one records of this mapping are secondary lines."""
+    star, full = [], []
+    k = 0
+    rows = [ln.split("\t") for ln in sam_text.split("\n") if ln and not ln.startswith("@")]
+    # (the drop-in's bin filter can drop a read's primary line and leave secondary ones: those keep their SEQ)
+    donors = {(f[0], int(f[1]) & 0xC0) for f in rows if not int(f[1]) & 0x904 and f[9] != "*" and "H" not in f[5]}
+    for f in rows:
+        ln = "\t".join(f)
+        full.append(ln)
+        if int(f[1]) & 0x100 and not int(f[1]) & 0x4 and f[9] != "*" and (f[0], int(f[1]) & 0xC0) in donors:
+            k += 1
+            if k % 3 == 0:
+                ln = "\t".join(f[:9] + ["*", "*"] + f[11:])
+        star.append(ln)
+    return star, full
+
+
+def time_restore(argv, sam_text, names, reads, n_lr):
+    from proovread_amd import _abi, bamio, cns
+    star, full = strip_secondaries(sam_text)
+    n_sec = sum(1 for ln in star if ln.split("\t")[9] == "*")
+    bodies = {k: bamio._native_sort(bamio._native_encode("".join(x + "\n" for x in v), names))
+              for k, v in (("on", star), ("off", full))}
+    ctx = _abi.default_context()
+    L = _abi.lib()
+    dr = cns.pack_reads(reads)
+    r2l = np.arange(n_lr, dtype=np.int32)
+    cb = _abi.CnsBatch()
+    cb.n_lr = n_lr
+    cb.lr_off = _abi.ptr(dr["lr_off"], C.c_int64)
+    cb.ref_seq = _abi.ptr(dr["ref_seq"], C.c_uint8)
+    cb.ref_qual = _abi.ptr(dr["ref_qual"], C.c_uint8)
+    kernel_ms = {"on": [], "off": []}
+    info = {}
+
+    def run(which):
+        body = bodies[which]
+        nk, nr = C.c_int64(), C.c_int64()
+        if which == "on":
+            _abi.check(L.pr_cns_upload_bam_opts(ctx.h, C.byref(cb), body, len(body), _abi.ptr(r2l, C.c_int32), n_lr,
+                                                _abi.PR_BAM_RESTORE_SEQ, C.byref(nk), C.byref(nr)), "pr_cns_upload_bam_opts")
+            info["restored"] = int(nr.value)
+        else:
+            _abi.check(L.pr_cns_upload_bam(ctx.h, C.byref(cb), body, len(body), _abi.ptr(r2l, C.c_int32), n_lr, C.byref(nk)),
+                       "pr_cns_upload_bam")
+        ms = C.c_double()
+        _abi.check(L.pr_bam_decode_last_ms(ctx.h, C.byref(ms)), "pr_bam_decode_last_ms")
+        kernel_ms[which].append(ms.value)
+        info["kept_" + which] = int(nk.value)
+
+    on_ms, on_all = median_ms(lambda: run("on"))
+    off_ms, off_all = median_ms(lambda: run("off"))
+    rec = {"records": len(star), "secondaries_without_seq": n_sec, "restored": info["restored"], "kept_on": info["kept_on"],
+           "kept_off": info["kept_off"], "long_reads": n_lr, "bam_body_bytes_on": len(bodies["on"]),
+           "bam_body_bytes_off": len(bodies["off"]),
+           "decode_kernels_ms_restore_on": round(statistics.median(kernel_ms["on"][1:]), 3),
+           "decode_kernels_ms_restore_off_restored_stream": round(statistics.median(kernel_ms["off"][1:]), 3),
+           "upload_bam_wall_ms_restore_on": on_ms, "upload_bam_wall_ms_restore_off_restored_stream": off_ms,
+           "runs_ms": {"on": on_all, "off": off_all, "on_kernels": [round(x, 3) for x in kernel_ms["on"][1:]],
+                       "off_kernels": [round(x, 3) for x in kernel_ms["off"][1:]]}}
+    print(json.dumps(rec, indent=1))
+    if argv:
+        Path(argv[0]).parent.mkdir(parents=True, exist_ok=True)
+        Path(argv[0]).write_text(json.dumps(rec, indent=1) + "\n")
+
+
 def main():
     from proovread_amd import _abi, bam2cns, bamio, bwa_proovread, cns, synth
     from proovread_amd import tasks as T
+    argv = [a for a in sys.argv[1:] if a != "--restore"]
+    restore = "--restore" in sys.argv[1:]
     gl, n_lr = 460_000, 1_380
     d = synth.simulate_reads(20261015 + 2, gl, n_lr, 10_000, int(round(15.0 * gl / 150)), threads=16)
     asc = np.frombuffer(b"ACGTN", np.uint8)
@@ -57,9 +136,11 @@ def main():
         rc = bwa_proovread.mem(["-b", "20", "-l", "300"] + T.bwa_argv("bwa-sr-1") + ["-t", "16", str(lr_fa), str(sr_fq)],
                                out=out, log=io.StringIO())
         assert rc == 0
+    reads = [cns.LongRead(n, s, "5" * len(s)) for n, s in zip(names, lr)]
+    if restore:
+        return time_restore(argv, out.getvalue(), names, reads, n_lr)
     body = bamio._native_sort(bamio._native_encode(out.getvalue(), names))
     del out
-    reads = [cns.LongRead(n, s, "5" * len(s)) for n, s in zip(names, lr)]
     ctx = _abi.default_context()
     L = _abi.lib()
     L.pr_bam_decode_alns.argtypes = [C.c_char_p, C.c_int64, C.c_int, C.POINTER(bam2cns._BamAlns)]
@@ -127,9 +208,9 @@ def main():
            "kernel_hbm_fraction": round(moved / (k_ms * 1e-3) / HBM_BYTES_PER_S, 4),
            "runs_ms": {"a": a_all, "b": b_all, "b_kernels": [round(x, 3) for x in kernel_ms[1:]], "c": c_all}}
     print(json.dumps(rec, indent=1))
-    if len(sys.argv) > 1:
-        Path(sys.argv[1]).parent.mkdir(parents=True, exist_ok=True)
-        Path(sys.argv[1]).write_text(json.dumps(rec, indent=1) + "\n")
+    if argv:
+        Path(argv[0]).parent.mkdir(parents=True, exist_ok=True)
+        Path(argv[0]).write_text(json.dumps(rec, indent=1) + "\n")
 
 
 if __name__ == "__main__":
