@@ -471,6 +471,10 @@ int pr_seed_gpu_lane_ticks(pr_ctx *ctx, uint64_t *ticks6);
 /* pass 1's occurrence tables (profiling): 100 MHz wave-clock ticks summed over
    waves of the start pass, the hit pass and the count table */
 int pr_seed_gpu_occ_ticks(pr_ctx *ctx, uint64_t *ticks3);
+/* the chaining kernel (profiling): ticks summed over waves (x 64, as lane ticks) of its phases:
+   the chunks brought on chip with the lanes' lists, the lane chaining, the weights and the list
+   past -W, the rank sort, -D, the tasks' bases, the tasks */
+int pr_seed_gpu_chain_ticks(pr_ctx *ctx, uint64_t *ticks7);
 /* pass 2 (profiling): reads chained on one lane (occurrences beyond the wave's slots), then
    ticks summed over waves of the wave-parallel chaining, of the one-lane chaining and of the
    chain filter; then the largest ticks of one read's occurrence table, of its SMEMs and of the

@@ -487,7 +487,7 @@ int map_buffers(SeedMap &M, const pr_seed_opts *o, const uint8_t *sr_seq, bool i
         (rc = D[SB_SCRATCH].ensure((size_t)scratch)) ||
         (rc = D[SB_OUT].ensure((size_t)(std::min<int64_t>(M.chunk, n_sr) * slot_bytes + 16))) ||
         (rc = D[SB_NOUT].ensure((size_t)n_sr * 4 + 16)) || (rc = D[SB_STATUS].ensure((size_t)n_sr * 4 + 16)) ||
-        (rc = D[SB_NEXT].ensure(256)) || (rc = D[SB_PRE].ensure(((size_t)n_sr + 1) * 8)) ||
+        (rc = D[SB_NEXT].ensure(512)) || (rc = D[SB_PRE].ensure(((size_t)n_sr + 1) * 8)) ||
         (rc = D[SB_DENSE].ensure(sizeof(pr_seed_task))) || (M.occ_words && (rc = D[SB_OCC].ensure((size_t)M.occ_words * 8))))
         return rc;
     K.sr_seq = D[SB_SEQ].as<uint8_t>();
@@ -499,7 +499,7 @@ int map_buffers(SeedMap &M, const pr_seed_opts *o, const uint8_t *sr_seq, bool i
     K.prof = reinterpret_cast<unsigned long long *>(D[SB_NEXT].as<uint8_t>() + 64);
     // (next[1], next[2]: the chaining launches' counters; next[4..5]: the occurrence pool's cursor)
     K.occ = seedc::OccPool{D[SB_OCC].as<uint64_t>(), reinterpret_cast<unsigned long long *>(K.next + 4), M.occ_words};
-    HIPCHK(hipMemsetAsync(K.next, 0, 256, s));
+    HIPCHK(hipMemsetAsync(K.next, 0, 512, s));
     return 0;
 }
 
@@ -846,6 +846,14 @@ extern "C" int pr_seed_gpu_pass2_ticks(pr_ctx *c, uint64_t *t7) {
     if (!c->sd[SB_NEXT].p) return set_error(PR_ERR_ARG, "no pr_seed_gpu_map launch yet");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipMemcpy(t7, c->sd[SB_NEXT].as<uint8_t>() + 64 + 13 * 8, 56, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int pr_seed_gpu_chain_ticks(pr_ctx *c, uint64_t *ticks7) {
+    if (!c || !ticks7) return set_error(PR_ERR_ARG, "null arg");
+    if (!c->sd[SB_NEXT].p) return set_error(PR_ERR_ARG, "no pr_seed_gpu_map launch yet");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpy(ticks7, c->sd[SB_NEXT].as<uint8_t>() + 64 + 24 * 8, 56, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -11,7 +11,10 @@
 // on its own (LDS atomics only where the order cannot matter), and a phase ends with the wave's
 // LDS synchronisation.  On the device `lane` is the thread's lane and a phase runs once; on the
 // host `lane` is a loop index, 0 .. 63 one after the other, so a native program runs exactly the
-// device's decisions.  Values every lane needs live in ChainLds::sv.
+// device's decisions.  Counters every lane adds to live in ChainLds::sv.  Code between the phases is
+// run by every lane with the same values (the host: once); values that cross lanes there -- a
+// ballot, a scan, one lane's value -- go through scc_ballot / scc_scan / scc_bcast below, and a
+// value a lane keeps from one phase to the next is a LaneReg.
 //
 // Chains of different (long read, strand) ranges never interact (seed_core.h chain_seq): the
 // ranges are dealt to lanes by a hash of their key and every lane chains its ranges' occurrences
@@ -44,6 +47,41 @@ template <class T> __device__ inline T scc_cas(T *p, T c, T v) {   // -> the val
 #define SCC_CAS(p, c, v) ::prgpu::seedc::scc_cas(p, c, v)
 #define SCC_NOW() __builtin_amdgcn_s_memrealtime()
 #define SCC_STAT(L, k) ((void)0)
+// Cross-lane values.  A LaneReg is a value of each lane that lives across phases (a register; the
+// host keeps all 64), read and written as r.at(lane) inside SCC_LANES.  The operations below are
+// called between phases, by every lane (the host: once), with the lane's value as a function of
+// the lane; what they return is the same in every lane unless it is written to a LaneReg.
+namespace prgpu {
+namespace seedc {
+__device__ inline int scc_lane() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+template <class T> struct LaneReg {
+    T v;
+    __device__ T &at(int) { return v; }
+    __device__ const T &at(int) const { return v; }
+};
+// bit l: f(l) != 0
+template <class F> __device__ inline uint64_t scc_ballot(F f) { return __builtin_amdgcn_ballot_w64(f(scc_lane()) ? true : false); }
+// lane src's value (src the same in every lane)
+__device__ inline int scc_bcast(const LaneReg<int> &r, int src) { return __builtin_amdgcn_readlane(r.v, src); }
+__device__ inline uint64_t scc_bcast(const LaneReg<uint64_t> &r, int src) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)r.v, src);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(r.v >> 32), src);
+    return (uint64_t)hi << 32 | lo;
+}
+// ex.at(l) = f(0) + .. + f(l - 1); -> the sum over all lanes
+template <class F> __device__ inline int scc_scan(LaneReg<int> &ex, F f) {
+    const int lane = scc_lane(), v = f(lane);
+    int x = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int y = __builtin_amdgcn_ds_bpermute((lane - d) << 2, x);   // (lane - d's x)
+        if (lane >= d) x += y;
+    }
+    ex.v = x - v;
+    return __builtin_amdgcn_readlane(x, 63);
+}
+}  // namespace seedc
+}  // namespace prgpu
 #else
 // host only: how often a case occurred in the read (ChainLds::sv, SV_TIES ..), for the tests
 #define SCC_STAT(L, k) (++(L).sv[k])
@@ -54,6 +92,25 @@ namespace seedc {
 template <class T> inline T scc_add(T *p, T v) { const T o = *p; *p = (T)(o + v); return o; }
 template <class T> inline T scc_or(T *p, T v) { const T o = *p; *p = (T)(o | v); return o; }
 template <class T> inline T scc_cas(T *p, T c, T v) { const T o = *p; if (o == c) *p = v; return o; }
+// the cross-lane values' host twins: every lane's value before any lane uses the result
+template <class T> struct LaneReg {
+    T v[64];
+    T &at(int lane) { return v[lane]; }
+    const T &at(int lane) const { return v[lane]; }
+};
+template <class F> inline uint64_t scc_ballot(F f) {
+    uint64_t m = 0;
+    for (int lane = 0; lane < 64; ++lane) m |= f(lane) ? 1ull << lane : 0ull;
+    return m;
+}
+inline int scc_bcast(const LaneReg<int> &r, int src) { return r.v[src & 63]; }
+inline uint64_t scc_bcast(const LaneReg<uint64_t> &r, int src) { return r.v[src & 63]; }
+template <class F> inline int scc_scan(LaneReg<int> &ex, F f) {
+    int v[64], x = 0;
+    for (int lane = 0; lane < 64; ++lane) v[lane] = f(lane);   // (f may read ex)
+    for (int lane = 0; lane < 64; ++lane) ex.v[lane] = x, x += v[lane];
+    return x;
+}
 }  // namespace seedc
 }  // namespace prgpu
 #define SCC_ADD(p, v) ::prgpu::seedc::scc_add(p, v)
@@ -181,7 +238,7 @@ struct ChainLds {
     int16_t chead[S], ctail[S], cn[S];   // chains: first and last seed, seeds
     int16_t cnx[S];    //        the next chain of its range; after the chaining the chain's weight
     uint16_t cidx[S];  //        the stream index of the occurrence that opened it
-    int16_t ts[S];     // output: a task's seed
+    int16_t ts[S];     // output: a task's seed; before the sort: the weights by pl index
     union {
         struct {
             int32_t key[HT];   // rid * 2 + strand (-1: free)
@@ -189,28 +246,32 @@ struct ChainLds {
             uint64_t hfr[CH];  // the occurrences being chained
             uint32_t ql[CH];
             int16_t idx[CH];   // the lanes' lists of them
-            uint8_t own[CH];   // their owner lanes
         } ch;
         struct {
             int16_t pl[S];     // the chains past -W, any order; after the sort a task's chain
             int16_t sch[S];    // the same sorted (weight desc, pos, cidx)
             int16_t kept[S];   // by sorted index
-            int16_t fm[S];     // kept list: the first chain it shadowed (-1: none)
-            int16_t kb[S], ke[S], kw[S];   // kept list: query interval, weight; kw before the sort:
-                                           // the weights by pl index; kb / ke after -D: task base, chain number
+            int16_t fm[S];     // kept list from its 64th entry: the first chain it shadowed (-1: none)
+            int16_t kb[S], ke[S], kw[S];   // after the sort: the chains' query intervals and weights by sorted
+                                           // index; -D packs the kept list into them in place (entry k <= the
+                                           // chain's sorted index; the first 64 entries are kept in registers);
+                                           // kb / ke after -D: task base, chain number
         } po;
     } u;
     int32_t cnt[64], cur[64];
     int32_t sv[16];      // wave-uniform values (SV_*)
-    uint32_t mk[2][4];   // -D: [set][ov lo, ov hi, br lo, br hi] of the step's 64 kept chains
 };
 enum {
-    SV_ERR = 0, SV_NRG, SV_NP, SV_NK, SV_LARGE, SV_DROP, SV_NO, SV_STEP, SV_NS, SV_NC,
+    SV_ERR = 0, SV_NRG, SV_NP, SV_NS, SV_NC,
     // host build only (SCC_STAT): sort ties that creation order decided, chains opened before the
     // head / between two chains / after the tail of a range that had chains, chains whose
     // reference cover is below their query cover
     SV_TIES, SV_INS_HEAD, SV_INS_MID, SV_INS_TAIL, SV_WR_LT
 };
+
+// chain_read's phases (its ticks): the chunks on chip with the lanes' lists, the lane chaining, the
+// weights and the list past -W, the rank sort, -D, the tasks' bases, the tasks
+enum { CT_LOAD = 0, CT_LANES, CT_WEIGHTS, CT_SORT, CT_DROP, CT_BASE, CT_TASKS, CT_N };
 
 SC_HD uint32_t range_hash(int32_t key) { return (uint32_t)key * 0x9E3779B1u; }
 
@@ -218,7 +279,7 @@ SC_HD uint32_t range_hash(int32_t key) { return (uint32_t)key * 0x9E3779B1u; }
 // calls it (the host: once).  -> 0 or SC_OVER_SEEDS / SC_OVER_CHAINS / SC_OVER_OUT, *n_out the tasks.
 // lim_seeds / lim_chains: the capacities of the pass the read comes from (Caps.seeds / .chains),
 // which hold here as in its lane chaining: the same reads as before go on to the later passes.
-// ticks (device, optional): wall-clock ticks [chaining, mem_chain_flt, output] added by the wave.
+// ticks (device, optional): wall-clock ticks added by the wave, by CT_* below.
 template <int S, int HT, int CH>
 SC_HD int chain_read(const IndexView &I, const pr_seed_opts &O, ChainLds<S, HT, CH> &L, const uint64_t *g_hfr,
                      const uint32_t *g_ql, int n, int len, int sid, pr_seed_task *out, int cap_out, int *n_out,
@@ -247,47 +308,86 @@ SC_HD int chain_read(const IndexView &I, const pr_seed_opts &O, ChainLds<S, HT, 
     // 0. empty table, counters
     SCC_LANES {
         if (lane < 16) L.sv[lane] = 0;
-        if (lane < 8) L.mk[lane >> 2][lane & 3] = 0u;
         for (int k = lane; k < HT; k += 64) L.u.ch.key[k] = -1;
     }
     SCC_END;
+    // a chunk's words are loaded while the chunk before it is chained (a lane holds G of each)
+    constexpr int G = CH / 64;
+    LaneReg<uint64_t> nh[G];
+    LaneReg<uint32_t> nq[G];
+    auto fetch = [&](int c0) {
+        SCC_LANES {
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const int e = c0 + g * 64 + lane;
+                nh[g].at(lane) = e < n ? g_hfr[e] : 0ull;
+                nq[g].at(lane) = e < n ? g_ql[e] : 0u;
+            }
+        }
+    };
+    fetch(0);
     for (int c0 = 0; c0 < n && !L.sv[SV_ERR]; c0 += CH) {
         const int m = n - c0 < CH ? n - c0 : CH;
-        // 1. the next occurrences on chip (coalesced), their owner lanes and the lanes' shares
-        SCC_LANES { L.cnt[lane] = 0; }
-        SCC_END;
+        // 1. the chunk on chip, its occurrences' owner lanes
+        LaneReg<int> own[G], pos[G], add[G], cur;
         SCC_LANES {
-            for (int e = lane; e < m; e += 64) {
-                const uint64_t v = g_hfr[c0 + e];
-                L.u.ch.hfr[e] = v;
-                L.u.ch.ql[e] = g_ql[c0 + e];
-                const int rid = (int)(v & ((1u << FR_RID_BITS) - 1u));
-                const int32_t key = rid * 2 + ((int64_t)(v >> FR_RID_BITS) >= l_pac ? 1 : 0);
-                const int o = (int)(range_hash(key) >> 26);
-                L.u.ch.own[e] = (uint8_t)o;
-                SCC_ADD(&L.cnt[o], 1);
-            }
-            for (int e = m + lane; e < ((m + 7) & ~7); e += 64) L.u.ch.own[e] = 255;
-        }
-        SCC_END;
-        SCC_LANES {
-            int x = 0;
-            for (int t = 0; t < lane; ++t) x += L.cnt[t];
-            L.cur[lane] = x;
-        }
-        SCC_END;
-        // the lanes' lists in stream order: every lane scans the owners, 8 a load
-        SCC_LANES {
-            int c = L.cur[lane];
-            for (int e0 = 0; e0 < m; e0 += 8) {
-                uint64_t w;
-                __builtin_memcpy(&w, L.u.ch.own + e0, 8);
+            L.cnt[lane] = 0;
 #pragma unroll
-                for (int u = 0; u < 8; ++u)
-                    if ((int)((w >> (8 * u)) & 0xFF) == lane) L.u.ch.idx[c++] = (int16_t)(e0 + u);
+            for (int g = 0; g < G; ++g) {
+                const int e = g * 64 + lane;
+                own[g].at(lane) = -1;
+                pos[g].at(lane) = add[g].at(lane) = 0;
+                if (e < m) {
+                    const uint64_t v = nh[g].at(lane);
+                    L.u.ch.hfr[e] = v;
+                    L.u.ch.ql[e] = nq[g].at(lane);
+                    const int rid = (int)(v & ((1u << FR_RID_BITS) - 1u));
+                    const int32_t key = rid * 2 + ((int64_t)(v >> FR_RID_BITS) >= l_pac ? 1 : 0);
+                    own[g].at(lane) = (int)(range_hash(key) >> 26);
+                }
             }
         }
         SCC_END;
+        if (c0 + CH < n) fetch(c0 + CH);
+        // the lanes' lists in stream order, 64 occurrences a step: the lanes with a lane's owner
+        // from six ballots; an occurrence's place in its owner's list is the owner's count so far
+        // plus the lanes before it with the same owner
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            if (g * 64 >= m) break;
+            uint64_t bit[6];
+#pragma unroll
+            for (int b = 0; b < 6; ++b) bit[b] = scc_ballot([&](int lane) { return (own[g].at(lane) >> b) & 1; });
+            const uint64_t valid = scc_ballot([&](int lane) { return own[g].at(lane) >= 0; });
+            SCC_LANES {
+                const int o = own[g].at(lane);
+                if (o >= 0) {
+                    uint64_t same = valid;
+#pragma unroll
+                    for (int b = 0; b < 6; ++b) same &= ((o >> b) & 1) ? bit[b] : ~bit[b];
+                    const int before = __builtin_popcountll(same & ((1ull << lane) - 1ull));
+                    pos[g].at(lane) = L.cnt[o] + before;
+                    add[g].at(lane) = before ? 0 : __builtin_popcountll(same);   // (the first of them counts them)
+                }
+            }
+            SCC_END;
+            SCC_LANES {
+                if (add[g].at(lane)) L.cnt[own[g].at(lane)] += add[g].at(lane);
+            }
+            SCC_END;
+        }
+        scc_scan(cur, [&](int lane) { return (int)L.cnt[lane]; });
+        SCC_LANES { L.cur[lane] = cur.at(lane); }
+        SCC_END;
+        SCC_LANES {
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const int o = own[g].at(lane);
+                if (o >= 0) L.u.ch.idx[L.cur[o] + pos[g].at(lane)] = (int16_t)(g * 64 + lane);
+            }
+        }
+        SCC_END;
+        SCC_TICK(CT_LOAD);
         // 2. every lane chains its occurrences in order (chain_seq's decisions)
         SCC_LANES {
             const int first = L.cur[lane], mine = L.cnt[lane];
@@ -384,9 +484,9 @@ SC_HD int chain_read(const IndexView &I, const pr_seed_opts &O, ChainLds<S, HT, 
             }
         }
         SCC_END;
+        SCC_TICK(CT_LANES);
     }
     if (L.sv[SV_ERR]) return L.sv[SV_ERR];
-    SCC_TICK(0);
     const int ncv = L.sv[SV_NC];
     // 3. mem_chain_flt: the weights (seed_core.h chain_weight), the chains past -W listed
     // (any order: the sort's keys are distinct).  The range table is dead from here.
@@ -417,133 +517,174 @@ SC_HD int chain_read(const IndexView &I, const pr_seed_opts &O, ChainLds<S, HT, 
             if (w >= O.min_chain_weight) {
                 const int m = SCC_ADD(&L.sv[SV_NP], 1);
                 L.u.po.pl[m] = (int16_t)c;
-                L.u.po.kw[m] = (int16_t)w;
+                L.ts[m] = (int16_t)w;
             }
         }
     }
     SCC_END;
     const int nch = L.sv[SV_NP];
+    SCC_TICK(CT_WEIGHTS);
     const bool keep_all = O.drop_ratio <= 0;
     // the stable weight sort as ranks: a chain's place is the number of smaller keys
-    SCC_LANES {
-        for (int m = lane; m < nch; m += 64) {
-            const int c = L.u.po.pl[m], w = L.u.po.kw[m];
-            const int64_t ps = rbeg(L.chead[c]);
-            const int ix = L.cidx[c];
-            int rank = 0;
-            for (int j = 0; j < nch; ++j) {
-                const int wj = L.u.po.kw[j];
-                if (wj > w) ++rank;
-                else if (wj == w) {
-                    const int cj = L.u.po.pl[j];
-                    const int64_t pj = rbeg(L.chead[cj]);
-                    rank += (pj < ps || (pj == ps && (int)L.cidx[cj] < ix)) ? 1 : 0;
-                    if (pj == ps && cj != c) SCC_STAT(L, SV_TIES);
+    // ((32767 - weight) << 40 | pos, then cidx).  64 chains a step hold their keys in registers
+    // (a lane each) and count the keys below theirs as those come by, a lane after the other
+    auto sort_key = [&](int m, uint64_t &a, int &x) {
+        a = ~0ull, x = 0;
+        if (m < nch) {
+            const int c = L.u.po.pl[m];
+            a = (uint64_t)(32767 - L.ts[m]) << 40 | (uint64_t)rbeg(L.chead[c]);
+            x = L.cidx[c];
+        }
+    };
+    for (int m0 = 0; m0 < nch; m0 += 64) {
+        LaneReg<uint64_t> ka, ja;
+        LaneReg<int> kx, jx, rk;
+        SCC_LANES {
+            sort_key(m0 + lane, ka.at(lane), kx.at(lane));
+            rk.at(lane) = 0;
+        }
+        for (int j0 = 0; j0 < nch; j0 += 64) {
+            const int mj = nch - j0 < 64 ? nch - j0 : 64;
+            SCC_LANES { sort_key(j0 + lane, ja.at(lane), jx.at(lane)); }
+            for (int jj = 0; jj < mj; ++jj) {
+                const uint64_t a = scc_bcast(ja, jj);
+                const int x = scc_bcast(jx, jj);
+                SCC_LANES {
+                    rk.at(lane) += (a < ka.at(lane) || (a == ka.at(lane) && x < kx.at(lane))) ? 1 : 0;
+                    if (a == ka.at(lane) && j0 + jj != m0 + lane) SCC_STAT(L, SV_TIES);
                 }
             }
-            L.u.po.sch[rank] = (int16_t)c;
-            L.u.po.kept[rank] = keep_all ? 3 : 0;
+        }
+        SCC_LANES {
+            const int m = m0 + lane;
+            if (m < nch) {
+                const int c = L.u.po.pl[m], rank = rk.at(lane);
+                L.u.po.sch[rank] = (int16_t)c;
+                L.u.po.kept[rank] = keep_all ? 3 : 0;
+                if (!keep_all) {   // -D's view of the chain
+                    const int tl = L.ctail[c];
+                    L.u.po.kb[rank] = (int16_t)qb(L.chead[c]);
+                    L.u.po.ke[rank] = (int16_t)(qb(tl) + sl(tl));
+                    L.u.po.kw[rank] = L.ts[m];
+                }
+            }
         }
     }
     SCC_END;
-    // -D / mask_level (seed_core.h chain_flt): sorted order, the kept list 64 entries a step over
-    // the lanes; the lowest lane that drops the chain is the sequential loop's break
+    SCC_TICK(CT_SORT);
+    // -D / mask_level (seed_core.h chain_flt) in sorted order.  The chains come 64 at a time into
+    // registers (a lane each) and one after the other to every lane; the kept list is tested 64
+    // entries a step, entry k by lane k & 63: the first 64 from registers, the later ones from
+    // kb / ke / kw [k], where they were packed (k <= the chain's sorted index, which was read
+    // before).  The lowest lane that drops the chain is the sequential loop's break.  The kept
+    // list's length, `large` and `drop` are the same in every lane: they follow from the ballots.
     if (nch > 0 && !keep_all) {
-        SCC_LANES {
-            if (lane == 0) {
-                const int c = L.u.po.sch[0], hd = L.chead[c], tl = L.ctail[c];
-                const int w0 = L.cnx[c];
-                L.u.po.kb[0] = (int16_t)qb(hd);
-                L.u.po.ke[0] = (int16_t)(qb(tl) + sl(tl));
-                L.u.po.kw[0] = (int16_t)w0;
-                L.u.po.fm[0] = -1;
-                L.u.po.kept[0] = 3;
-                L.sv[SV_NK] = 1;
-                L.sv[SV_LARGE] = L.sv[SV_DROP] = 0;
-                L.sv[SV_STEP] = 0;
+        LaneReg<int> rb, re, rw, rfm;   // kept entries 0 .. 63: query interval, weight, the first chain it shadowed
+        LaneReg<int> cb, ce, cw, cv;    // the step's chains; cv: kept as (0: dropped)
+        SCC_LANES { rb.at(lane) = re.at(lane) = rw.at(lane) = 0, rfm.at(lane) = -1; }
+        int nk = 0;
+        for (int i0 = 0; i0 < nch; i0 += 64) {
+            const int mi = nch - i0 < 64 ? nch - i0 : 64;
+            SCC_LANES {
+                const bool in = lane < mi;
+                cb.at(lane) = in ? L.u.po.kb[i0 + lane] : 0;
+                ce.at(lane) = in ? L.u.po.ke[i0 + lane] : 0;
+                cw.at(lane) = in ? L.u.po.kw[i0 + lane] : 0;
+                cv.at(lane) = 0;
             }
-        }
-        SCC_END;
-        for (int i = 1; i < nch; ++i) {
-            const int ci = L.u.po.sch[i], hi = L.chead[ci], ti = L.ctail[ci];
-            const int bi = qb(hi), ei = qb(ti) + sl(ti), wi = L.cnx[ci];
-            for (int k0 = 0; k0 < L.sv[SV_NK] && !L.sv[SV_DROP]; k0 += 64) {
-                const int set = L.sv[SV_STEP] & 1;
-                SCC_LANES {
-                    const int k = k0 + lane;
-                    if (k < L.sv[SV_NK]) {
-                        const int bj = L.u.po.kb[k], ej = L.u.po.ke[k], wj = L.u.po.kw[k];
-                        const int bmax = bj > bi ? bj : bi;
-                        const int emin = ej < ei ? ej : ei;
-                        if (emin > bmax) {
-                            const int li = ei - bi, lj = ej - bj;
-                            const int minl = li < lj ? li : lj;
-                            if (emin - bmax >= minl * O.mask_level && minl < O.max_chain_gap) {
-                                SCC_OR(&L.mk[set][lane >> 5], 1u << (lane & 31));
-                                if (wi < wj * O.drop_ratio && wj - wi >= O.min_seed_len << 1)
-                                    SCC_OR(&L.mk[set][2 + (lane >> 5)], 1u << (lane & 31));
+            SCC_END;
+            for (int j = 0; j < mi; ++j) {
+                const int i = i0 + j;
+                const int bi = scc_bcast(cb, j), ei = scc_bcast(ce, j), wi = scc_bcast(cw, j);
+                bool large = false, drop = false;
+                for (int k0 = 0; k0 < nk && !drop; k0 += 64) {
+                    LaneReg<int> hit;   // 1: overlaps past mask_level, 2: and drops the chain
+                    SCC_LANES {
+                        const int k = k0 + lane;
+                        int h = 0;
+                        if (k < nk) {
+                            const int bj = k0 ? L.u.po.kb[k] : rb.at(lane), ej = k0 ? L.u.po.ke[k] : re.at(lane);
+                            const int wj = k0 ? L.u.po.kw[k] : rw.at(lane);
+                            const int bmax = bj > bi ? bj : bi;
+                            const int emin = ej < ei ? ej : ei;
+                            if (emin > bmax) {
+                                const int li = ei - bi, lj = ej - bj;
+                                const int minl = li < lj ? li : lj;
+                                if (emin - bmax >= minl * O.mask_level && minl < O.max_chain_gap) {
+                                    h = 1;
+                                    if (wi < wj * O.drop_ratio && wj - wi >= O.min_seed_len << 1) h = 3;
+                                }
+                            }
+                        }
+                        hit.at(lane) = h;
+                    }
+                    const uint64_t ov = scc_ballot([&](int lane) { return hit.at(lane) & 1; });
+                    const uint64_t br = scc_ballot([&](int lane) { return hit.at(lane) & 2; });
+                    const int last = br ? ctz64(br) : 63;   // the lanes the sequential loop visits
+                    const uint64_t seen = ov & (last >= 63 ? ~0ull : ((2ull << last) - 1ull));
+                    SCC_LANES {
+                        if ((seen >> lane) & 1ull) {
+                            if (k0 == 0) {
+                                if (rfm.at(lane) < 0) rfm.at(lane) = i;
+                            } else if (L.u.po.fm[k0 + lane] < 0) {
+                                L.u.po.fm[k0 + lane] = (int16_t)i;
                             }
                         }
                     }
+                    large = large || seen != 0;
+                    drop = br != 0;
                 }
-                SCC_END;
+                if (drop) continue;
                 SCC_LANES {
-                    const uint64_t ov = (uint64_t)L.mk[set][0] | ((uint64_t)L.mk[set][1] << 32);
-                    const uint64_t br = (uint64_t)L.mk[set][2] | ((uint64_t)L.mk[set][3] << 32);
-                    const int last = br ? ctz64(br) : 63;   // the lanes the sequential loop visits
-                    const uint64_t seen = ov & (last >= 63 ? ~0ull : ((2ull << last) - 1ull));
-                    if (((seen >> lane) & 1ull) && L.u.po.fm[k0 + lane] < 0) L.u.po.fm[k0 + lane] = (int16_t)i;
-                    if (lane == 63) {   // (the last lane: on the host every other lane has read the masks)
-                        if (seen) L.sv[SV_LARGE] = 1;
-                        if (br) L.sv[SV_DROP] = 1;
-                        L.sv[SV_STEP] = set ^ 1;
-                        L.mk[set ^ 1][0] = L.mk[set ^ 1][1] = L.mk[set ^ 1][2] = L.mk[set ^ 1][3] = 0u;
-                    }
-                }
-                SCC_END;
-            }
-            SCC_LANES {
-                if (lane == 0) {
-                    if (!L.sv[SV_DROP]) {
-                        const int nk = L.sv[SV_NK];
+                    if (lane == j) cv.at(lane) = large ? 2 : 3;
+                    if (nk < 64) {
+                        if (lane == nk) rb.at(lane) = bi, re.at(lane) = ei, rw.at(lane) = wi, rfm.at(lane) = -1;
+                    } else if (lane == 0 && nk < S) {   // (always: nk < nch <= S)
                         L.u.po.kb[nk] = (int16_t)bi;
                         L.u.po.ke[nk] = (int16_t)ei;
                         L.u.po.kw[nk] = (int16_t)wi;
                         L.u.po.fm[nk] = -1;
-                        L.u.po.kept[i] = L.sv[SV_LARGE] ? 2 : 3;
-                        L.sv[SV_NK] = nk + 1;
                     }
-                    L.sv[SV_LARGE] = L.sv[SV_DROP] = 0;
                 }
+                if (nk >= 64) SCC_END;
+                ++nk;
+            }
+            SCC_LANES {
+                if (lane < mi && cv.at(lane)) L.u.po.kept[i0 + lane] = (int16_t)cv.at(lane);
             }
             SCC_END;
         }
         SCC_LANES {
-            for (int k = lane; k < L.sv[SV_NK]; k += 64)
+            if (lane < nk && rfm.at(lane) >= 0) L.u.po.kept[rfm.at(lane)] = 1;
+            for (int k = 64 + lane; k < nk && k < S; k += 64)
                 if (L.u.po.fm[k] >= 0) L.u.po.kept[L.u.po.fm[k]] = 1;
         }
         SCC_END;
     }
-    SCC_TICK(1);
+    SCC_TICK(CT_DROP);
     // 4. the tasks (seed_core.h map_output without mem_flt_chained_seeds): a kept chain's tasks
-    // start after those of the kept chains before it
-    SCC_LANES {
-        if (lane == 0) {
-            int no = 0, nkept = 0;
-            for (int i = 0; i < nch; ++i) {
-                if (L.u.po.kept[i] == 0) {
-                    L.u.po.kb[i] = -1;
-                    continue;
-                }
-                L.u.po.kb[i] = (int16_t)no;
-                L.u.po.ke[i] = (int16_t)nkept++;
-                no += L.cn[L.u.po.sch[i]];
+    // start after those of the kept chains before it (a scan over the chains, 64 a step)
+    int no = 0, nkept = 0;
+    for (int i0 = 0; i0 < nch; i0 += 64) {
+        LaneReg<int> ex;
+        const int tot = scc_scan(ex, [&](int lane) {
+            const int i = i0 + lane;
+            return i < nch && L.u.po.kept[i] != 0 ? (int)L.cn[L.u.po.sch[i]] : 0;
+        });
+        const uint64_t kp = scc_ballot([&](int lane) { return i0 + lane < nch && L.u.po.kept[i0 + lane] != 0; });
+        SCC_LANES {
+            const int i = i0 + lane;
+            if (i < nch) {
+                const bool mine = (kp >> lane) & 1ull;
+                L.u.po.kb[i] = (int16_t)(mine ? no + ex.at(lane) : -1);
+                if (mine) L.u.po.ke[i] = (int16_t)(nkept + __builtin_popcountll(kp & ((1ull << lane) - 1ull)));
             }
-            L.sv[SV_NO] = no;
         }
+        no += tot;
+        nkept += __builtin_popcountll(kp);
     }
     SCC_END;
-    const int no = L.sv[SV_NO];
+    SCC_TICK(CT_BASE);
     if (no > cap_out) return SC_OVER_OUT;
     // every task's chain and seed, chain list order
     SCC_LANES {
@@ -599,7 +740,7 @@ SC_HD int chain_read(const IndexView &I, const pr_seed_opts &O, ChainLds<S, HT, 
         }
     }
     SCC_END;
-    SCC_TICK(2);
+    SCC_TICK(CT_TASKS);
 #undef SCC_TICK
     *n_out = no;
     return 0;

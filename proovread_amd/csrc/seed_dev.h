@@ -19,9 +19,10 @@ struct SeedDev {
     int64_t stride;            // seedc::scratch_bytes(caps), 8-byte multiple
     int64_t n_lanes;           // scratch slots = resident waves (one read per wave at a time)
     int32_t *next;             // read counter the waves dequeue from (zeroed before the launch)
-    unsigned long long *prof;  // [8] wall-clock ticks summed over waves: occurrence tables, SMEMs
+    unsigned long long *prof;  // [56] wall-clock ticks summed over waves: occurrence tables, SMEMs
                                // (pass 1: the whole lane-per-read phase), chaining and filter +
-                               // output of pass 2 (may be null)
+                               // output of pass 2, ...; [24 .. 30]: seed_chain_kernel's phases
+                               // (seed_chain.h CT_*) (may be null)
     seedc::Caps caps;
     pr_seed_task *out;         // [(reads of the chunk) * caps.out]: read i's slots at (i - out0) * caps.out
     int64_t out0;              // first read of the chunk (pass 1 maps reads [*next, n_sr) at entry)

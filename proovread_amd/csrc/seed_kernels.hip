@@ -1130,14 +1130,19 @@ __global__ void __launch_bounds__(64) seed_chain_kernel(SeedDev D) {
     __shared__ LDS L;
     const int lane = threadIdx.x;
     const int64_t nlim = D.rlist ? D.n_list : D.n_sr - D.out0;
-    unsigned long long ct[3] = {0ULL, 0ULL, 0ULL};   // chaining, mem_chain_flt, output
+    unsigned long long ct[seedc::CT_N] = {};   // chain_read's phases
     for (;;) {
         int j0 = 0;
         if (lane == 0) j0 = atomicAdd(D.next + (SECOND ? 2 : 1), 64);
         j0 = __shfl(j0, 0, 64);
         if (j0 >= nlim) {   // every wave reaches this: the grid drains
-            if (D.prof && lane == 0)
-                for (int k = 0; k < 3; ++k) atomicAdd(&D.prof[4 + 3 + k], ct[k] * 64ULL);   // (as lane-summed ticks)
+            if (D.prof && lane == 0) {   // (as lane-summed ticks) chaining, mem_chain_flt, output; then their parts
+                using namespace seedc;
+                atomicAdd(&D.prof[7], (ct[CT_LOAD] + ct[CT_LANES]) * 64ULL);
+                atomicAdd(&D.prof[8], (ct[CT_WEIGHTS] + ct[CT_SORT] + ct[CT_DROP]) * 64ULL);
+                atomicAdd(&D.prof[9], (ct[CT_BASE] + ct[CT_TASKS]) * 64ULL);
+                for (int k = 0; k < CT_N; ++k) atomicAdd(&D.prof[24 + k], ct[k] * 64ULL);
+            }
             break;
         }
         // a lane per read: which of the 64 are this launch's

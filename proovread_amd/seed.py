@@ -235,6 +235,13 @@ def _phase_ms(L, ctx) -> dict:
         L.pr_seed_gpu_occ_ticks.argtypes = [C.c_void_p, C.c_void_p]
         _abi.check(L.pr_seed_gpu_occ_ticks(ctx.h, ot.ctypes.data), "pr_seed_gpu_occ_ticks")
         out["occ_table_parts"] = {k: round(float(v) / 1e5, 1) for k, v in zip(("starts", "hits", "count_table"), ot)}
+    if hasattr(L, "pr_seed_gpu_chain_ticks"):
+        ct = np.zeros(7, np.uint64)
+        L.pr_seed_gpu_chain_ticks.argtypes = [C.c_void_p, C.c_void_p]
+        _abi.check(L.pr_seed_gpu_chain_ticks(ctx.h, ct.ctypes.data), "pr_seed_gpu_chain_ticks")
+        out["chain_kernel_ms_summed"] = {k: round(float(v) / 1e5, 1) for k, v in
+                                         zip(("load_owner_lists", "lane_chaining", "weights_listing", "rank_sort", "drop_pass",
+                                              "task_base", "tasks"), ct)}
     if hasattr(L, "pr_seed_gpu_pass2_ticks"):
         t2 = np.zeros(7, np.uint64)
         L.pr_seed_gpu_pass2_ticks.argtypes = [C.c_void_p, C.c_void_p]
