@@ -620,6 +620,9 @@ int pr_lrset_index(pr_ctx *ctx, int which);
 int pr_iter_upload_lrset(pr_ctx *ctx, const pr_sw_batch *b);
 int pr_lrset_commit(pr_ctx *ctx, pr_comm *comm, int flags);
 int pr_lrset_download(pr_ctx *ctx, int64_t *off, uint8_t *seq, uint8_t *qual, uint8_t *map);
+/* pr_lrset_set_map: the mapping reference from the host, one byte per base in the set's layout
+ * (ccs-1: the masked copy of ccseq's output, bin/proovread:876-882) */
+int pr_lrset_set_map(pr_ctx *ctx, const uint8_t *map);
 /* pr_lrset_snapshot: a device copy of the set's current reads and qualities (the read-long
  * output); pr_lrset_restore: the set returns to it, the mapping reference to the reads -- a
  * correction run restarted on the same input without a host round trip (bench.py: every step
@@ -908,6 +911,77 @@ int pr_siam_extend_host(const pr_siam_aligner *al, const uint8_t *q, int32_t qle
                         int32_t h0, int32_t *out);
 int pr_siam_extend_gpu(pr_ctx *ctx, const pr_siam_aligner *al, const uint8_t *q, const int64_t *q_off,
                        const uint8_t *t, const int64_t *t_off, const int32_t *h0, int32_t n, int32_t *out);
+
+/* ------------------------------------------------------------------ */
+/* ccs-1 (bin/ccseq; bin/proovread:871-895): the subreads of one ZMW collapsed into one read.
+ * Grouping and output are restated from ccseq:237-329, the consensus from Sam::Seq with ccseq's
+ * settings (Seq.pm:232-467, 1568-1654 with use_ref_qual and qual_weighted).  REPLACES the
+ * `bwa-proovread index` / `mem` calls of ccs_chunk (ccseq:339-449) with rules of its own: exact
+ * seeds vote for an orientation and a diagonal, one banded local alignment per subread follows
+ * (parity with bwa unpinned).  Sequences are ASCII, A C G T N only, qualities
+ * phred + 33.                                                                               */
+typedef struct pr_ccs_params {
+    int32_t k, w;              /* -k 9 minimum seed length, -w 300 band half width      */
+    int32_t a, b;              /* -A 5 -B 11 (any N scores -1)                           */
+    int32_t o_del, o_ins;      /* -O 2,1                                                 */
+    int32_t e_del, e_ins;      /* -E 4,3                                                 */
+    int32_t trim;              /* Sam::Seq->Trim(1)                                      */
+    int32_t min_aln_length;    /* StateMatrixMinAlnLength 50                             */
+    int32_t phred_offset;      /* 33                                                     */
+    int32_t reserved;
+    double indel_taboo;        /* Sam::Seq->InDelTaboo(0.001); InDelTabooLength unset    */
+} pr_ccs_params;
+enum { PR_CCS_SECONDARY = 0, PR_CCS_PRIMARY = 1, PR_CCS_SINGLE = 2 };
+enum {                                   /* per-group status: the reference subread is written unchanged */
+    PR_CCS_TOO_LONG = 1,                 /* a subread longer than PR_CCS_MAX_LEN            */
+    PR_CCS_TOO_MANY = 2,                 /* more than PR_CCS_MAX_SUBREADS subreads          */
+    PR_CCS_BAD_ALN = 4,                  /* pr_ccs_cns: a supplied alignment is malformed or leaves the reference */
+};
+#define PR_CCS_MAX_LEN 16384
+#define PR_CCS_MAX_SUBREADS 64
+#define PR_CCS_MAX_BAND 512              /* largest w */
+enum { PR_CCS_ID_OK = 0, PR_CCS_ID_NOT_SUBREAD = 1, PR_CCS_ID_NOT_UNIQUE = 2 };
+/* Groups of subreads.  Subreads grp_off[g] .. grp_off[g+1] form group g (consecutive, >= 2),
+ * grp_ref[g] is its reference subread (an absolute index).  Subread s is seq / qual
+ * [off[s], off[s+1]).  cig_off gives each subread's CIGAR slot (at least its length + the
+ * reference's + 2 ops), out_off each group's output slot (at least the summed length of its
+ * subreads), shared by sequence, quality and trace.                                         */
+typedef struct pr_ccs_batch {
+    int32_t n_groups, n_sub;
+    const int32_t *grp_off, *grp_ref;
+    const int64_t *off;
+    const uint8_t *seq, *qual;
+    const int64_t *cig_off, *out_off;
+} pr_ccs_batch;
+/* one alignment per subread onto its group's reference (none for the reference itself): POS
+ * 0-based, CIGAR ops len << 4 | op with M 0, I 1, D 2, S 4, of the subread in the aligned
+ * orientation (strand 1: reverse complement, qualities reversed)                            */
+typedef struct pr_ccs_alns {
+    int32_t *mapped, *strand, *pos, *score, *n_cigar;   /* [n_sub] */
+    uint32_t *cigar;                                     /* slots of cig_off */
+} pr_ccs_alns;
+typedef struct pr_ccs_out {
+    int32_t *status, *seq_len, *trace_len;   /* [n_groups] */
+    uint8_t *seq, *qual, *trace;             /* slots of out_off */
+} pr_ccs_out;
+void pr_ccs_params_default(pr_ccs_params *p);
+/* ccseq:237-299 over n ids (id r = ids[id_off[r] .. id_off[r+1])): role[n] gets PR_CCS_PRIMARY
+ * for the reference subread of a group (ccseq:356-363), PR_CCS_SINGLE for a subread alone in
+ * its ZMW, PR_CCS_SECONDARY otherwise (a lone last record included, ccseq:296-299); group[n]
+ * the group's index or -1; len[n] the sequence lengths ccseq:358 compares.  *bad_kind / *bad_index name the first id ccseq dies on.         */
+int pr_ccs_group(int32_t n, const char *ids, const int64_t *id_off, const int32_t *len, int32_t *role, int32_t *group,
+                 int32_t *n_groups, int32_t *bad_kind, int32_t *bad_index);
+/* The stage: every subread mapped to its group's reference, then each group's consensus.
+ * ctx NULL: host (n_threads, <= 0: all cores).  A group over a capacity gets a status flag and
+ * no consensus; the call succeeds.  pr_ccs_map and pr_ccs_cns are the two halves (test hooks):
+ * pr_ccs_cns takes the alignments it is given.                                             */
+int pr_ccs_run(pr_ctx *ctx, const pr_ccs_params *p, const pr_ccs_batch *b, int n_threads, pr_ccs_alns *alns,
+               pr_ccs_out *out);
+int pr_ccs_map(pr_ctx *ctx, const pr_ccs_params *p, const pr_ccs_batch *b, int n_threads, pr_ccs_alns *alns);
+int pr_ccs_cns(pr_ctx *ctx, const pr_ccs_params *p, const pr_ccs_batch *b, int n_threads, const pr_ccs_alns *alns,
+               pr_ccs_out *out);
+/* device milliseconds (HIP events around the kernels) of the context's last pr_ccs_* call */
+int pr_ccs_last_ms(pr_ctx *ctx, double *ms);
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,9 @@ hot stages on the device:
   bwa-sr-finish    (proovread:838-850, 1572-1577) 30x sampling, finish scoring,
                    unmasked reference, --no-use-ref-qual, --max-ins-length 0,
                    --detect-chimera
+  ccs-1            (proovread:871-895; modes sr / mr) every ZMW's subreads collapsed into one
+                   read (ccseq.py, pr_ccs_*), the masked output the first mapping reference;
+                   ids that are no subread ids fall back to the -noccs list (proovread:1512-1517)
   read-sam / read-bam  (proovread:718-736; modes sam / bam, --sam / --bam) alignments made
                    elsewhere: one consensus of every long read over the file, its BAM
                    records decoded and grouped per read on the device (cns.run_bam)
@@ -73,7 +76,7 @@ class LoopConfig:
     sampling: bool = True                  # --no-sampling turns it off
     min_sr_length: Optional[int] = None    # proovread:530-532 (None: shortest short read)
     lr_min_length: Optional[int] = None    # cfg lr-min-length (None: 2 * min_sr_length)
-    mode: Optional[str] = None             # sr-noccs / mr-noccs; None: by short-read length (proovread:636-642)
+    mode: Optional[str] = None             # sr-noccs / mr-noccs, sr / mr (with ccs-1); None: by short-read length (proovread:636-642)
     tasks: Optional[Tuple[str, ...]] = None   # None: the mode's task list (proovread.cfg:105-127)
     seed_threads: int = 0
     bin_filter: bool = True                # bwa-proovread -b/-l in every iteration (proovread:1302-1313)
@@ -143,6 +146,7 @@ class TaskLog:
     stage_ms: Optional[Dict[str, float]] = None   # ... per stage (index, seeding, SW, hand-off, consensus)
     part_ms: Optional[Dict[str, float]] = None    # host wall clock per part of the device task (GpuStages)
     pre_ms: Optional[float] = None         # the task's host time before the stages are called
+    counters: Optional[Dict[str, int]] = None     # ccs-1: single, primary, secondary (ccseq:324-328), flagged groups
 
 
 @dataclasses.dataclass
@@ -571,6 +575,36 @@ class GpuStages:
         self.load(LongReads(cur.ids, [r.seq.encode("latin-1") for r in res], [r.qual.encode("latin-1") for r in res]))
         return TaskOut(int(sum(len(r.kept) for r in res)), [ln for r in res for ln in r.chim_lines()])
 
+    def set_map(self, masked: Sequence[bytes]) -> None:
+        """The mapping reference of the next task from the host (pr_lrset_set_map)."""
+        from . import _abi
+        L = _abi.lib()
+        L.pr_lrset_set_map.argtypes = [C.c_void_p, C.c_void_p]
+        pool = np.frombuffer(b"".join(masked) + b"\0", np.uint8).copy()
+        if len(pool) - 1 != int(self.lrs.offsets()[-1]):
+            raise ValueError("the mapping reference must have the reads' layout")
+        _abi.check(L.pr_lrset_set_map(self.ctx.h, pool.ctypes.data), "pr_lrset_set_map")
+
+    def ccs(self, reads: LongReads, mask_cfg: Tuple[str, int], keep: Optional[str] = None) -> Tuple[LongReads, Dict[str, int]]:
+        """The task ccs-1 (bin/proovread:871-895) on the read-long output: ccseq (ccseq.py; the
+        pr_ccs_* kernels), its output as the resident long reads, their --phred-mask masking
+        (hcr-mask of ccs-1 scaled by the short-read length, through the mask stage) as the
+        mapping reference of the first bwa task.  keep: ccseq's output is left as
+        `keep`.ccs-1.fq.  -> (the reads, ccseq's counters)."""
+        from . import ccseq, mask, seqfilter
+        recs = [(i, "", s, q) for i, s, q in zip(reads.ids, reads.seqs, reads.quals)]
+        out, stats = ccseq.ccs_records(recs, ctx=self.ctx)
+        self.device_ms += stats.pop("kernel_ms", 0.0)
+        if keep:
+            with open(f"{keep}.ccs-1.fq", "wb") as f:
+                f.write(b"".join(seqfilter.format_record(r, False, 0) for r in out))
+        new = LongReads([r[0] for r in out], [bytes(r[2]) for r in out], [bytes(r[3]) for r in out])
+        self.load(new)
+        if new.ids:
+            masked, _, _ = mask.run(new.seqs, new.quals, mask.params(*mask_cfg), ctx=self.ctx)
+            self.set_map(masked)
+        return new, stats
+
     def reads(self) -> LongReads:
         off, seq, qual, _ = self.lrs.download(seq=True, qual=True)
         return LongReads(self.ids, pools=(seq, off, qual))
@@ -654,6 +688,13 @@ def _write_task_fq(pre: str, task: str, reads: LongReads) -> None:
         f.write(reads.fastq())
 
 
+def subread_ids(ids) -> bool:
+    """Every id is a PacBio subread id, ^(m[^/]+/\\d+)/(\\d+_\\d+) (bin/proovread:1406-1408, ccseq:238)."""
+    import re
+    pat = re.compile(r"^(m[^/]+/\d+)/(\d+_\d+)")
+    return all(pat.match(i) for i in ids)
+
+
 def mode_of(cfg: LoopConfig) -> Optional[str]:
     """bin/proovread:628-632: --bam selects mode bam, --sam mode sam, whatever --mode says;
     otherwise --mode, or None (by short-read length, proovread:636-642)."""
@@ -678,6 +719,12 @@ def run(lr_records: Sequence[Tuple[str, bytes, Optional[bytes]]], sr_data: bytes
     stubby = cfg.lr_min_length if cfg.lr_min_length is not None else 2 * min_sr
     mode = mode_of(cfg) or T.mode_for(min_sr)
     tasks = list(cfg.tasks or T.MODE_TASKS[mode])
+    if "noccs" not in mode and any(t.startswith("ccs-") for t in tasks) and not subread_ids(r[0] for r in lr_records):
+        # bin/proovread:1512-1517: ids that are no PacBio subread ids (stubby reads count too)
+        mode = T.noccs_mode(mode)
+        if mode not in T.MODE_TASKS:
+            raise ValueError(f"unknown mode {mode}")
+        tasks = list(T.MODE_TASKS[mode])
     ids: List[str] = []
     ignored: List[str] = []
     log: List[TaskLog] = []
@@ -691,6 +738,19 @@ def run(lr_records: Sequence[Tuple[str, bytes, Optional[bytes]]], sr_data: bytes
         if cfg.keep_temporary:
             _write_task_fq(cfg.keep_temporary, "read-long", reads)
         tasks = tasks[1:]
+        if tasks and tasks[0].startswith("ccs-"):   # proovread:871-895 (every rank runs the whole stage)
+            if not hasattr(stages, "ccs"):
+                raise ValueError(f"task {tasks[0]} needs the device stages")
+            ent = TaskLog(tasks[0])
+            t_task = time.perf_counter()
+            dev0 = getattr(stages, "device_ms", None)
+            reads, ent.counters = stages.ccs(reads, (hcr_mask_for(tasks[0]), min_sr), cfg.keep_temporary)
+            ids = reads.ids
+            ent.wall_ms = round((time.perf_counter() - t_task) * 1e3, 1)
+            if dev0 is not None:
+                ent.device_ms = round(stages.device_ms - dev0, 1)
+            log.append(ent)
+            tasks = tasks[1:]
     chim, last_masked, tlog = run_tasks(stages, srs, tasks, cfg, mode, min_sr, bool(ids), comm)
     log += tlog
     reads = stages.reads() if ids else LongReads([], [], [])

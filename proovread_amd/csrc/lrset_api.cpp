@@ -81,6 +81,19 @@ extern "C" int pr_lrset_download(pr_ctx *c, int64_t *off, uint8_t *seq, uint8_t 
     return 0;
 }
 
+extern "C" int pr_lrset_set_map(pr_ctx *c, const uint8_t *map) {
+    if (!c || c->ls_n < 0) return set_error(PR_ERR_ARG, "no resident long-read set (pr_lrset_load)");
+    const size_t nb = (size_t)c->ls_off.back();
+    if (nb && !map) return set_error(PR_ERR_ARG, "null arg");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    int rc;
+    if ((rc = upload(c->ls[LS_MAP], map, nb, s))) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    c->ls_map_is_reads = false;
+    return 0;
+}
+
 extern "C" int pr_lrset_index(pr_ctx *c, int which) {
     if (!c || c->ls_n < 0) return set_error(PR_ERR_ARG, "no resident long-read set (pr_lrset_load)");
     if (which != PR_LRSET_MAP && which != PR_LRSET_READS) return set_error(PR_ERR_ARG, "which: PR_LRSET_MAP / _READS");

@@ -6,7 +6,8 @@ proovread.cfg is a Perl hash; bin/proovread looks values up with `cfg(KEY, TASK)
 counter, else DEF wins.  This module restates the entries the sr / mr correction loop
 reads, with their cfg lines:
 
-  mode-tasks      proovread.cfg:105-132 (sr-noccs, mr-noccs; sam, bam: alignments made elsewhere)
+  mode-tasks      proovread.cfg:105-132 (sr, mr with ccs-1; sr-noccs, mr-noccs; sam, bam: alignments
+                  made elsewhere)
   detect-chimera  proovread.cfg:205-211
   bwa-*           proovread.cfg:318-365 (bwa mem options per task)
   sr-coverage     proovread.cfg:188-192
@@ -25,6 +26,9 @@ import re
 from typing import Dict, List, Tuple
 
 MODE_TASKS: Dict[str, Tuple[str, ...]] = {
+    # PacBio subreads: ccs-1 collapses each ZMW's subreads first (proovread.cfg:107-109; ccseq.py)
+    "sr": ("read-long", "ccs-1", "bwa-sr-1", "bwa-sr-2", "bwa-sr-3", "bwa-sr-4", "bwa-sr-5", "bwa-sr-6", "bwa-sr-finish"),
+    "mr": ("read-long", "ccs-1", "bwa-mr-1", "bwa-mr-2", "bwa-mr-3", "bwa-mr-4", "bwa-mr-5", "bwa-mr-6", "bwa-mr-finish"),
     "sr-noccs": ("read-long", "bwa-sr-1", "bwa-sr-2", "bwa-sr-3", "bwa-sr-4", "bwa-sr-5", "bwa-sr-6", "bwa-sr-finish"),
     "mr-noccs": ("read-long", "bwa-mr-1", "bwa-mr-2", "bwa-mr-3", "bwa-mr-4", "bwa-mr-5", "bwa-mr-6", "bwa-mr-finish"),
     # external alignments (--sam / --bam, proovread.cfg:130-132; bin/proovread:170, 718-736)
@@ -79,6 +83,12 @@ def cfg_task(table: dict, task: str):
 def mode_for(min_sr_length: int) -> str:
     """bin/proovread:636-642: `mr` beyond 150 bp short reads (noccs: no PacBio subreads)."""
     return "mr-noccs" if min_sr_length > 150 else "sr-noccs"
+
+
+def noccs_mode(mode: str) -> str:
+    """bin/proovread:1512-1517: the mode a run falls back to when the long reads' ids are no
+    PacBio subread ids (`sr` -> `sr-noccs`)."""
+    return re.sub(r"^([^-]+)", r"\1-noccs", mode)
 
 
 def is_finish(task: str) -> bool:
