@@ -983,6 +983,81 @@ int pr_ccs_cns(pr_ctx *ctx, const pr_ccs_params *p, const pr_ccs_batch *b, int n
 /* device milliseconds (HIP events around the kernels) of the context's last pr_ccs_* call */
 int pr_ccs_last_ms(pr_ctx *ctx, double *ms);
 
+/* ------------------------------------------------------------------ */
+/* The unitig consensus: `bam2cns --utg-mode` (bin/proovread:1536-1586), the generate_consensus
+ * of bam2cns:375-455 in unitig mode for a batch of long reads.  Alignments are added without
+ * bins (bam2cns:349-351), filtered (Seq.pm:919-927, 949-999, 1001-1047), and the consensus is
+ * Sam::Seq's (Seq.pm:714-734, 232-467, 1568-1654) with the overlap windows of bam2cns:398-422
+ * among the ignored ranges.  DESIGN.md §14 states the rules.  Sequences are ASCII (anything
+ * but A C G T counts as N), qualities phred + phred_offset.                                */
+typedef struct pr_utg_params {
+    int32_t trim;                 /* cfg sr-trim                                            */
+    int32_t indel_taboo_length;   /* cfg sr-indel-taboo-length, 0: the fraction below       */
+    int32_t min_aln_length;       /* StateMatrixMinAlnLength 50                             */
+    int32_t phred_offset;         /* 33: alignment qualities and the output                 */
+    int32_t ref_phred_offset;     /* --qv-offset: the reference's qualities                 */
+    int32_t max_ins_length;       /* --max-ins-length, 0 off (Seq.pm:1607)                  */
+    int32_t fallback_phred;       /* --fallback-phred for a QUAL of '*' (Seq.pm:281-284)    */
+    int32_t qual_weighted;        /* --qual-weighted                                        */
+    int32_t use_ref_qual;         /* --[no-]use-ref-qual                                    */
+    int32_t invert_scores;        /* --invert-scores (Alignment.pm:529)                     */
+    int32_t has_min_ncscore;      /* --min-ncscore given (bam2cns:394)                      */
+    int32_t has_rep_coverage;     /* --rep-coverage given (bam2cns:395)                     */
+    int32_t rep_coverage;
+    int32_t reserved;
+    double indel_taboo;           /* cfg sr-indel-taboo                                     */
+    double min_ncscore;
+} pr_utg_params;
+enum {                                   /* per-read status: no output for the read          */
+    PR_UTG_TOO_LONG = 1,                 /* longer than PR_UTG_MAX_LEN                       */
+    PR_UTG_TOO_MANY = 2,                 /* more than PR_UTG_MAX_ALNS alignments             */
+    PR_UTG_BAD_ALN = 4,                  /* an alignment the reference dies on: an op other than M I D
+                                            inside the clips, a zero-length op, CIGAR / SEQ lengths that
+                                            differ, columns beyond the read, ncscore of length 0 */
+};
+#define PR_UTG_MAX_LEN 262144
+#define PR_UTG_MAX_ALNS 4096
+/* Read r is ref_seq / ref_qual [read_off[r], read_off[r+1]) (ref_qual NULL: a FASTA reference,
+ * no reference weights) and has the alignments [aln_off[r], aln_off[r+1]) in file order.
+ * Alignment a: POS pos[a] (1-based), AS score[a] if has_score[a], SEQ / QUAL [seq_off[a],
+ * seq_off[a+1]) (QUAL ignored unless has_qual[a]: a '*'), CIGAR ops [cig_off[a], cig_off[a+1]) as
+ * len << 4 | op in BAM's numbering.  ign: the MCR ranges of read r as (offset, length) pairs
+ * [ign_off[r], ign_off[r+1]).  out_off: output slots shared by sequence, quality and trace, at
+ * least the read's length plus the SEQ lengths of its alignments; win_off: window slots in
+ * pairs, at least max(alignments, 1) per read.                                             */
+typedef struct pr_utg_batch {
+    int32_t n_reads;
+    int32_t reserved;
+    int64_t n_alns;
+    const int64_t *read_off;
+    const uint8_t *ref_seq, *ref_qual;
+    const int64_t *aln_off;
+    const int32_t *pos;
+    const double *score;
+    const uint8_t *has_score, *has_qual;
+    const int64_t *seq_off;
+    const uint8_t *seq, *qual;
+    const int64_t *cig_off;
+    const uint32_t *cigar;
+    const int64_t *ign_off;
+    const int32_t *ign;
+    const int64_t *out_off, *win_off;
+} pr_utg_batch;
+typedef struct pr_utg_out {
+    int32_t *status, *seq_len, *trace_len, *n_win;   /* [n_reads] */
+    uint8_t *seq, *qual, *trace;                      /* slots of out_off */
+    uint8_t *kept;                                    /* [n_alns] 1: survived every filter */
+    int32_t *win;                                     /* the overlap windows (offset, length), slots of win_off */
+} pr_utg_out;
+/* bam2cns:375-455 with --utg-mode for every read of the batch.  ctx NULL: host (n_threads,
+ * <= 0: all cores).  A read over a capacity or with a malformed alignment gets a status flag
+ * and no output; its neighbours are exact and the call succeeds.                           */
+int pr_utg_run(pr_ctx *ctx, const pr_utg_params *p, const pr_utg_batch *b, int n_threads, pr_utg_out *out);
+/* device milliseconds (HIP events around the kernels) of the context's last pr_utg_run */
+int pr_utg_last_ms(pr_ctx *ctx, double *ms);
+/* ... by kernel, ms[5]: prep, coverage and windows, contained filter, consensus, output gather */
+int pr_utg_last_split(pr_ctx *ctx, double *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,10 @@ files (`PREFIX.fq`, `PREFIX.chim.tsv`, `PREFIX.ignored.tsv`,
 The consensus of every long read of the chunk is computed in ONE launch of
 libprgpu.so (pr_cns_run) instead of one Perl Sam::Seq object per read.
 
+With `--utg-mode` the job is the unitig consensus of the tasks blasr-utg / dazzler-utg /
+bwa-utg (utgcns.py: --qual-weighted, --rep-coverage, --min-ncscore, --fallback-phred,
+--invert-scores; `--host` runs it without a GPU).
+
 Alignment input: `--bam FILE` (coordinate-sorted BAM, read with a built-in
 BGZF/BAM reader: samtools is not needed) or `--sam FILE` (SAM text in the same
 order).  Errors exit with status 255 like Verbose->exit (Verbose.pm:454).
@@ -30,7 +34,7 @@ from typing import Dict, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import bamio, cns
+from . import bamio, cns, utgcns
 
 
 def _perl_split_digits(s: str) -> List[str]:
@@ -343,6 +347,7 @@ def parse_args(argv):
     ap.add_argument("--debug", dest="debug", action="store_true", default=False)
     ap.add_argument("--no-debug", dest="debug", action="store_false")
     ap.add_argument("--sr-min-length", action="store_true")
+    ap.add_argument("--host", action="store_true")   # --utg-mode only: the host path, no GPU
     args, _rest = ap.parse_known_args(argv)
     return args
 
@@ -379,6 +384,8 @@ class Job:
     prefix: str
     append: bool
     debug: bool
+    utg: Optional[utgcns.UtgParams] = None   # --utg-mode: the unitig consensus (utgcns) takes the job
+    host: bool = False
 
 
 def prepare(argv: Sequence[str]) -> Job:
@@ -386,10 +393,12 @@ def prepare(argv: Sequence[str]) -> Job:
     a = parse_args(list(argv))
     if not (a.bam or a.sam):
         die("BAM file required")
-    for flag, what in ((a.utg_mode, "--utg-mode"), (a.rep_coverage is not None, "--rep-coverage"),
-                       (a.min_ncscore is not None, "--min-ncscore"), (a.qual_weighted, "--qual-weighted")):
-        if flag:
-            die(f"{what} (utg/ccs modes) is not supported by the GPU consensus")
+    for flag, what in ((a.rep_coverage is not None, "--rep-coverage"), (a.min_ncscore is not None, "--min-ncscore"),
+                       (a.qual_weighted, "--qual-weighted"), (a.host, "--host")):
+        if flag and not a.utg_mode:
+            die(f"{what} needs --utg-mode: the binned consensus does not take it")
+    if a.utg_mode and a.detect_chimera:
+        die("--detect-chimera with --utg-mode: no task combines them (proovread.cfg:205-211)")
     if a.haplo_coverage:
         die("haploc_consensus??")   # bam2cns:432 dies the same way
     params = cns.CnsParams(
@@ -440,7 +449,16 @@ def prepare(argv: Sequence[str]) -> Job:
         for r in reads:
             r.desc = ""
     reads.sort(key=functools.cmp_to_key(lambda x, y: byfile_cmp(x.id, y.id)))
-    return Job(params, aln_path, "bam" if a.bam else "sam", reads, a.prefix, a.append, a.debug)
+    utg = None
+    if a.utg_mode:
+        # --coverage and --bin-size are read and unused: add_aln takes every alignment (bam2cns:349-351)
+        utg = utgcns.UtgParams(
+            trim=params.trim, indel_taboo_length=params.indel_taboo_length, indel_taboo=params.indel_taboo,
+            min_aln_length=params.min_aln_length, phred_offset=params.phred_offset, qv_offset=params.qv_offset,
+            max_ins_length=params.max_ins_length, fallback_phred=params.fallback_phred, qual_weighted=a.qual_weighted,
+            use_ref_qual=params.use_ref_qual, invert_scores=a.invert_scores, min_ncscore=a.min_ncscore,
+            rep_coverage=a.rep_coverage)
+    return Job(params, aln_path, "bam" if a.bam else "sam", reads, a.prefix, a.append, a.debug, utg, a.host)
 
 
 def execute(jobs: Sequence[Job]) -> None:
@@ -448,10 +466,11 @@ def execute(jobs: Sequence[Job]) -> None:
     into one GPU launch (one pass over the alignment file per batch)."""
     groups: Dict[tuple, List[Job]] = {}
     for j in jobs:
-        groups.setdefault((j.aln_path, j.aln_fmt, dataclasses.astuple(j.params)), []).append(j)
-    for (path, fmt, _), js in groups.items():
+        groups.setdefault((j.aln_path, j.aln_fmt, dataclasses.astuple(j.params),
+                           dataclasses.astuple(j.utg) if j.utg else None, j.host), []).append(j)
+    for (path, fmt, _, _, _), js in groups.items():
         reads = [r for j in js for r in j.reads]
-        if fmt == "bam" and reads and not os.environ.get("PRGPU_BAM2CNS_PYREADER"):
+        if fmt == "bam" and reads and not js[0].utg and not os.environ.get("PRGPU_BAM2CNS_PYREADER"):
             # one native pass over the BAM (inflate + decode in libprgpu), columns into pr_cns_batch
             try:
                 names, cols = bam_alns_native(path)
@@ -483,7 +502,13 @@ def execute(jobs: Sequence[Job]) -> None:
         for i, r in enumerate(reads):
             if want[r.id] != i:
                 alns[i] = alns[want[r.id]]
-        res = cns.run_chunk(reads, alns, js[0].params) if reads else []
+        if js[0].utg:
+            try:
+                res = utgcns.run(reads, alns, js[0].utg, device=not js[0].host)
+            except ValueError as e:
+                die(str(e))
+        else:
+            res = cns.run_chunk(reads, alns, js[0].params) if reads else []
         k = 0
         for j in js:
             write_outputs(j, res[k:k + len(j.reads)])
@@ -500,7 +525,7 @@ def write_outputs(j: Job, res: Sequence[cns.ReadResult]) -> None:
         try:
             for r in res:
                 if r.status != 0:
-                    die(f"{r.id}: consensus failed ({r.status})")
+                    die(f"{r.id}: consensus failed ({utgcns.status_name(r.status) if j.utg else r.status})")
                 fq.write(r.fastq)
                 if tr:
                     tr.write(r.fastq)

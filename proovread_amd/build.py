@@ -14,9 +14,9 @@ PKG = Path(__file__).resolve().parent
 SRC = PKG / "csrc"
 OBJ = PKG.parent / "build" / "obj"
 OUT = PKG / "libprgpu.so"
-SOURCES = ["cns_kernels.hip", "sw_kernels.hip", "pipe_kernels.hip", "pipe_big.hip", "xchg_kernels.hip", "mask_kernels.hip", "seed_kernels.hip", "seed_index.hip", "aln_kernels.hip", "siam_kernels.hip", "ccs_kernels.hip",
+SOURCES = ["cns_kernels.hip", "sw_kernels.hip", "pipe_kernels.hip", "pipe_big.hip", "xchg_kernels.hip", "mask_kernels.hip", "seed_kernels.hip", "seed_index.hip", "aln_kernels.hip", "siam_kernels.hip", "ccs_kernels.hip", "utg_kernels.hip",
            "bam_kernels.hip", "bam_enc_kernels.hip", "sw_api.cpp", "prgpu_api.cpp", "cns_api.cpp", "iter_api.cpp", "xchg_api.cpp", "mask_api.cpp", "lrset_api.cpp",
-           "seed_api.cpp", "siam_api.cpp", "ccs_api.cpp", "bam_api.cpp", "comm.cpp", "seed.cpp", "trim.cpp", "bam_codec.cpp", "fastq.cpp"]
+           "seed_api.cpp", "siam_api.cpp", "ccs_api.cpp", "utg_api.cpp", "bam_api.cpp", "comm.cpp", "seed.cpp", "trim.cpp", "bam_codec.cpp", "fastq.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-pthread",
          # exact IEEE double semantics of the reference Perl arithmetic
          "-ffp-contract=off", "-fno-fast-math",

@@ -351,37 +351,15 @@ struct ColEnt {
     double w;
 };
 
-CC_HD Prep prep_aln(const pr_ccs_params &p, const AlnView &a, int ref_len) {
-    Prep r = {-1, 0, 0, 0, 0, 0, 0};
+// the trim of State_matrix (Seq.pm:316-385) over the ops [cb, ce) left after the clips were
+// stripped, query window [wb, we); taboo_len: InDelTabooLength, 0 for the InDelTaboo fraction
+CC_HD Prep prep_trim(const pr_ccs_params &p, const AlnView &a, int ref_len, int cb, int ce, int wb, int we, int taboo_len) {
+    Prep r = {0, 0, 0, 0, 0, 0, 0};
     const int orig = a.q.len;
-    if (a.ncig <= 0) return r;
-    long qsum = 0;
-    for (int i = 0; i < a.ncig; ++i) {
-        const int op = (int)(a.cig[i] & 15), n = (int)(a.cig[i] >> 4);
-        if (n <= 0) return r;
-        if (op == OP_S) {
-            if (i != 0 && i != a.ncig - 1) return r;
-            qsum += n;
-        } else if (op == OP_M || op == OP_I) {
-            qsum += n;
-        } else if (op != OP_D) {
-            return r;
-        }
-    }
-    if (qsum != orig) return r;
-    r.use = 0;
-    if (!(orig > p.min_aln_length)) return r;   // Seq.pm:277
-    int cb = 0, ce = a.ncig, wb = 0, we = orig;
-    if ((a.cig[0] & 15) == OP_S) wb = (int)(a.cig[0] >> 4), cb = 1;
-    if (ce > cb && (a.cig[ce - 1] & 15) == OP_S) we -= (int)(a.cig[ce - 1] >> 4), --ce;
-    if (ce <= cb) {
-        r.use = -1;
-        return r;
-    }
     long rpos = a.pos;
     if (p.trim) {
         long mc = 0, dc = 0, ic = 0;
-        const long taboo = (long)((double)orig * p.indel_taboo + 0.5);
+        const long taboo = taboo_len ? (long)taboo_len : (long)((double)orig * p.indel_taboo + 0.5);
         for (int i = cb; i < ce; ++i) {
             const int op = (int)(a.cig[i] & 15);
             const long n = (long)(a.cig[i] >> 4);
@@ -423,6 +401,36 @@ CC_HD Prep prep_aln(const pr_ccs_params &p, const AlnView &a, int ref_len) {
     }
     r.use = (rpos < 0 || rpos + cols > ref_len || q != we - wb) ? -1 : 1;
     return r;
+}
+
+CC_HD Prep prep_aln(const pr_ccs_params &p, const AlnView &a, int ref_len) {
+    Prep r = {-1, 0, 0, 0, 0, 0, 0};
+    const int orig = a.q.len;
+    if (a.ncig <= 0) return r;
+    long qsum = 0;
+    for (int i = 0; i < a.ncig; ++i) {
+        const int op = (int)(a.cig[i] & 15), n = (int)(a.cig[i] >> 4);
+        if (n <= 0) return r;
+        if (op == OP_S) {
+            if (i != 0 && i != a.ncig - 1) return r;
+            qsum += n;
+        } else if (op == OP_M || op == OP_I) {
+            qsum += n;
+        } else if (op != OP_D) {
+            return r;
+        }
+    }
+    if (qsum != orig) return r;
+    r.use = 0;
+    if (!(orig > p.min_aln_length)) return r;   // Seq.pm:277
+    int cb = 0, ce = a.ncig, wb = 0, we = orig;
+    if ((a.cig[0] & 15) == OP_S) wb = (int)(a.cig[0] >> 4), cb = 1;
+    if (ce > cb && (a.cig[ce - 1] & 15) == OP_S) we -= (int)(a.cig[ce - 1] >> 4), --ce;
+    if (ce <= cb) {
+        r.use = -1;
+        return r;
+    }
+    return prep_trim(p, a, ref_len, cb, ce, wb, we, 0);
 }
 
 // min(Phreds2freqs(quals)) of the query bytes [qoff, qoff + n)

@@ -226,6 +226,8 @@ struct pr_ctx {
     float ms_index = 0.f;
     float ms_siam = 0.f;   // kernels of the last pr_siam_* call
     float ms_ccs = 0.f;    // kernels of the last pr_ccs_* call
+    float ms_utg = 0.f;    // kernels of the last pr_utg_run
+    float ms_utg_k[5] = {};   // ... by kernel: prep, coverage, contained filter, consensus, pack
     int64_t seed_n_text = 0, seed_n_hits = 0;
     int64_t seed_sr_bases = -1;   // bases of the short reads of the last pr_seed_gpu_map (SB_SEQ)
     bool iter_masked = false;
