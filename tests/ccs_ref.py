@@ -115,13 +115,14 @@ def score(p, r: str, q: str) -> int:
     return p["a"] if r == q else -p["b"]
 
 
-def align(R: str, Q: str, d0: int, p) -> Optional[Tuple[int, int, str]]:
-    """Banded local alignment around diagonal d0 -> (pos 0-based, score, CIGAR) or None."""
+def align(R: str, Q: str, d0: int, p, stats: Optional[dict] = None) -> Optional[Tuple[int, int, str]]:
+    """Banded local alignment around diagonal d0 -> (pos 0-based, score, CIGAR) or None.
+    stats, if given, receives n_best: the number of cells that hold the best score."""
     w = p["w"]
     H: Dict[Tuple[int, int], int] = {}
     E: Dict[Tuple[int, int], int] = {}   # E[(i, j)]: the deletion state arriving at (i, j)
     D: Dict[Tuple[int, int], Tuple[int, bool, bool, bool]] = {}
-    best, end = 0, None
+    best, end, n_best = 0, None, 0
     for i in range(len(R)):
         f = NEG
         for j in range(max(0, i - d0 - w), min(len(Q), i - d0 + w + 1)):
@@ -140,7 +141,10 @@ def align(R: str, Q: str, d0: int, p) -> Optional[Tuple[int, int, str]]:
             f = max(f - p["e_ins"], t)
             D[(i, j)] = (src, eext, fext, stop)
             if H[(i, j)] > best:
-                best, end = H[(i, j)], (i, j)
+                best, end, n_best = H[(i, j)], (i, j), 0
+            n_best += H[(i, j)] == best
+    if stats is not None:
+        stats["n_best"] = n_best if end is not None else 0
     if end is None:
         return None
     i, j = end

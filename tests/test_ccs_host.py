@@ -125,6 +125,169 @@ def test_mapping_clips_ns_and_no_seed():
         assert ga[4] is None and ga[5] is None   # no seed, no alignment
 
 
+# ---------------------------------------------------------------------------- mapping: built cases
+# Each case is checked twice from the restatement alone: that it reaches the edge it was built
+# for, and that the host path returns what the restatement returns.  tests/test_ccs_gpu.py runs
+# the same cases on the device.
+def _host_maps(case):
+    (ga,) = ccseq.map_groups([ccs_cases.pair_group(case)], ccseq.default_params(**case.over), device=False, threads=1)
+    assert ga[0] is None
+    assert ga[1] == ccs_cases.map_expected(case)
+    return ga[1]
+
+
+def _centre(case):
+    p = ccs_cases.ref_params(case)
+    return ccs_ref.centre(case.ref, case.query, p["k"], p["w"])
+
+
+def _best_cells(case):
+    """The number of band cells that hold the best score."""
+    rev, d0 = _centre(case)
+    stats = {}
+    ccs_ref.align(case.ref, ccs_ref.revcomp(case.query) if rev else case.query, d0, ccs_cases.ref_params(case), stats)
+    return stats["n_best"]
+
+
+def test_the_case_lists_name_every_case():
+    assert list(ccs_cases.band_cases()) == ccs_cases.BAND_NAMES
+    assert list(ccs_cases.band_edge_cases()) == ccs_cases.EDGE_NAMES
+    assert list(ccs_cases.overhang_cases()) == ccs_cases.OVERHANG_NAMES
+    assert list(ccs_cases.tie_cases()) == ccs_cases.TIE_NAMES
+    assert list(ccs_cases.tandem_cases()) == ccs_cases.TANDEM_NAMES
+    assert list(ccs_cases.seed_cases()) == ccs_cases.SEED_NAMES
+    assert list(ccs_cases.hand_cases()) == ccs_cases.HAND_NAMES
+
+
+@pytest.mark.parametrize("name", ccs_cases.BAND_NAMES)
+def test_band_gap_crosses_two_runs_of_the_scan(name):
+    """One gap of the full length between the flanks, at least two lanes' runs of cells long."""
+    case = ccs_cases.band_cases()[name]
+    w, n, op, strand = ccs_cases.band_shape(name)
+    assert case.over == {"w": w} and n >= 2 * ccs_cases.cells_per_lane(w) and n <= w
+    want = ccs_cases.map_expected(case)
+    assert want is not None and want[0] == strand
+    gaps = [int(x) for x, o in re.findall(r"(\d+)([MIDS])", want[3]) if o == op]
+    assert gaps == [n], want
+    _host_maps(case)
+
+
+@pytest.mark.parametrize("name", ccs_cases.EDGE_NAMES)
+def test_band_gap_opens_on_the_edge_of_the_band(name):
+    """The flank before the gap lies w diagonals from the centre: the insertion opens in the
+    band's first cell (lane 0's carry reaches the centre's lane), the deletion in its last."""
+    case = ccs_cases.band_edge_cases()[name]
+    w, kind = case.over["w"], name[name.index("_") + 1:]
+    rev, d0 = _centre(case)
+    want = ccs_cases.map_expected(case)
+    assert want is not None and want[0] == rev == int(kind == "rev")
+    gaps = [int(x) for x, o in re.findall(r"(\d+)([MIDS])", want[3]) if o == ("D" if kind == "del" else "I")]
+    assert gaps == [w] and w >= 2 * ccs_cases.cells_per_lane(w), want
+    # the flank before the gap starts at reference base 30 and query base 0: diagonal 30
+    assert want[1] == 30 and (30 - d0 == -w if kind == "del" else 30 - d0 == w)
+    _host_maps(case)
+
+
+def test_cells_per_lane_changes_where_the_bands_are():
+    assert [ccs_cases.cells_per_lane(w) for w in (8, 31, 32, 63, 64, 300, 512)] == [1, 1, 2, 2, 3, 10, 17]
+    assert 2 * 31 + 2 == 64   # w = 31: lane 63 holds the cell right of the band
+
+
+@pytest.mark.parametrize("name", ccs_cases.OVERHANG_NAMES)
+def test_band_overhangs_the_reference(name):
+    case = ccs_cases.overhang_cases()[name]
+    want = ccs_cases.map_expected(case)
+    rev, d0 = _centre(case)
+    w, lr, lq = case.over["w"], len(case.ref), len(case.query)
+    assert rev == 0 and want[0] == 0
+    if name.endswith("_end"):
+        assert d0 == lr - 60 > 0 and re.search(r"M40S$", want[3]) and not re.match(r"\d+S", want[3])
+        assert d0 - w > 0   # the rows start inside the reference, left of the query
+        assert (lr - 1) - d0 + w >= lq or w == 31   # at w = 64 the last row's band passes the query's end
+    else:
+        assert d0 == -40 < 0 and re.match(r"40S\d+M", want[3]) and not want[3].endswith("S")
+        assert -d0 - w < 0 or w == 31   # at w = 64 the first row's band starts left of the query
+        assert lq - 1 + d0 + w < lr - 1   # the band leaves the query before the reference ends
+    _host_maps(case)
+
+
+@pytest.mark.parametrize("name", ccs_cases.TIE_NAMES)
+def test_tie_scores(name):
+    """a = b = e = 1, o = 0: the best score is held by several cells, so the first in (i, j)
+    order has to be found, and M >= E >= F decides many cells."""
+    case = ccs_cases.tie_cases()[name]
+    assert len(case.ref) == len(case.query) == 150 and case.over == ccs_cases.TIE_SCORES
+    assert ccs_cases.map_expected(case) is not None
+    got = _host_maps(case)
+    if name == "unrelated":
+        assert _best_cells(case) >= 2
+    else:
+        assert "I" in got[3] and "D" in got[3] and got[2] >= 100
+
+
+@pytest.mark.parametrize("name", ccs_cases.TANDEM_NAMES)
+def test_tandem_repeat(name):
+    case = ccs_cases.tandem_cases()[name]
+    want = ccs_cases.map_expected(case)
+    assert want == (0, 20, 750, "150M")
+    # the same score one unit on: the first of several maximal cells wins
+    assert ccs_ref.map_ref(case.ref[50:], case.query, ccs_cases.ref_params(case))[2] == 750
+    if name == "w300":
+        assert _best_cells(case) >= 2   # all of them inside the band
+    if name == "w8":   # the bucket tie: equal pair sums several buckets apart
+        sums = ccs_cases.pair_sums(case)
+        top = sorted(k for k, v in sums.items() if v == max(sums.values()))
+        assert len(top) >= 2 and top[-1][1] - top[0][1] >= 2 and top[0][0] == 0
+    _host_maps(case)
+
+
+@pytest.mark.parametrize("name", ccs_cases.SEED_NAMES)
+def test_seed_cases(name):
+    case = ccs_cases.seed_cases()[name]
+    want = ccs_cases.map_expected(case)
+    fwd, rev = ccs_cases.both_seeds(case)
+    sums = ccs_cases.pair_sums(case)
+    w, lr, lq = ccs_cases.ref_params(case)["w"], len(case.ref), len(case.query)
+    if name.startswith("orient_tie"):
+        assert case.query == ccs_ref.revcomp(case.query)
+        best = max(sums.values())
+        assert {o for (o, _), v in sums.items() if v == best} == {0, 1}   # both orientations hold the maximum
+        assert want[0] == 0 and want[3] == "120M"
+        if name == "orient_tie_w1":
+            nb = ccs_cases.n_buckets(case)
+            assert 2 * nb > 512   # a thread of the 256 sees candidates of both orientations
+    elif name.startswith("key_tie"):
+        assert not rev and sorted(s[2] for s in fwd) == [9, 9, 12, 12, 12]
+        top = [s for s in fwd if s[2] == 12]
+        assert len({ccs_cases.dshift(case, s) // w for s in top}) == 1   # one bucket
+        assert len({s[0] - s[1] for s in top}) == 3                      # three diagonals
+        assert (len({s[0] for s in top}) == 3) == (name == "key_tie_i")  # decided by i, or by the diagonal alone
+        win = min(top, key=lambda s: (s[0], s[0] - s[1]))
+        assert _centre(case) == (0, win[0] - win[1])
+        p = ccs_cases.ref_params(case)
+        right = ccs_ref.align(case.ref, case.query, win[0] - win[1], p)
+        assert right == want[1:] and 60 <= right[1] < 118
+        for s in top:   # a band around either loser finds the beads: the choice shows in the result
+            if s != win:
+                assert ccs_ref.align(case.ref, case.query, s[0] - s[1], p)[1] >= 118
+    elif name == "one_9mer":
+        assert [s[2] for s in fwd + rev] == [9] and want is not None and want[0] == 0 and want[2] >= 45
+    elif name == "one_8mer":
+        assert fwd + rev == [] and want is None
+        assert case.ref[40:48] in case.query   # the 8-mer is there
+    elif name.startswith("diag_"):
+        assert lr + lq - 1 == int(name[5:]) and want is not None
+        assert want[0] == (name == "diag_256")
+    elif name.startswith("cand_"):
+        assert w == 1 and 2 * ccs_cases.n_buckets(case) == int(name[5:]) and want is not None
+        assert want[0] == (name != "cand_254") and want[3] == f"{lq}M"
+    else:
+        assert not rev and [s[2] for s in fwd] == [10, 9] and len({s[0] - s[1] for s in fwd}) == 1
+        assert ("N" in case.ref) == (name == "n_in_ref") and ("N" in case.query) == (name == "n_in_query")
+        assert want is not None and want[0] == 0 and want[2] >= 19 * 5 - 1
+    _host_maps(case)
+
+
 # ---------------------------------------------------------------------------- consensus
 def _oracle(case, **over):
     o = oracle_bind.run_case(case, **dict(ccs_cases.ORACLE_OVER, **over))
@@ -230,6 +393,76 @@ def test_malformed_alignments_are_flagged(hand):
         ga2[2] = (0, 5 if bad != "150M" else 20, 100, bad)
         (res,) = ccseq.consensus_groups([grp], [ga2], device=False)
         assert res[0] == ccseq.BAD_ALN and res[1] == b""
+
+
+@pytest.mark.parametrize("bad", ccs_cases.BAD_ALNS)
+def test_a_malformed_alignment_between_healthy_groups(hand, bad):
+    """The flagged group is empty; its neighbours in the batch are what they are alone."""
+    groups, alns, over_slot = ccs_cases.malformed_batch(hand, bad)
+    res = ccs_cases.consensus_raw(groups, alns, over_slot, device=False)
+    assert res[1] == (ccseq.BAD_ALN, b"", b"", b"")
+    for k in (0, 2):
+        assert res[k][0] == 0 and len(res[k][1]) > 100
+        assert [res[k]] == ccseq.consensus_groups([groups[k]], [alns[k]], device=False)
+    if bad == "over_slot":   # the count alone is wrong: the same alignment is healthy
+        assert ccs_cases.consensus_raw(groups, alns, (), device=False)[1][0] == 0
+
+
+@pytest.mark.parametrize("name", list(ccs_cases.TILES))
+def test_tile_boundary_cases(name):
+    """From the oracle: the gap and the three-base state stand in exactly the columns built,
+    so the sequence and the trace both differ in length from the reference."""
+    L, dels, inss = ccs_cases.TILES[name]
+    _, o = _check_case(name, *ccs_cases.tile_case(name))
+    assert o["trace"] == ccs_cases.tile_trace(name)
+    cols, at = [], 0   # the trace by column
+    for c in range(L):
+        n = 3 if c in inss else 1
+        cols.append(o["trace"][at:at + n])
+        at += n
+    assert all(cols[c] == "I" for c in dels) and all(cols[c] == "MDD" for c in inss)
+    assert [c for c in range(L) if cols[c] != "M"] == sorted(dels + inss)
+    assert len(o["fastq"].split("\n")[1]) == L - len(dels) + 2 * len(inss) != L
+    assert len(o["trace"]) == L + 2 * len(inss) != L
+    assert L <= 256 or any(c % 256 in (255, 0) for c in dels + inss)   # a choice on a tile's edge
+
+
+def test_tile_cases_cover_the_lengths():
+    assert {t[0] for t in ccs_cases.TILES.values()} >= {255, 256, 257, 512, 513}
+    assert (260, (255,), (256,)) in ccs_cases.TILES.values() and (516, (511,), (512,)) in ccs_cases.TILES.values()
+
+
+def test_more_cigar_ops_than_a_block_has_threads():
+    ref, rq, alns = ccs_cases.many_ops_case()
+    s, _, _, cig = alns[0]
+    assert len(re.findall(r"\d+[MID]", cig)) == 601
+    assert ccs_cases.kept_ops(cig, len(s)) == 601 > 256   # the taboo is one base: the 2M and the 20M at the ends stay
+    assert ccs_cases.kept_ops("299S350M1D349M1I1M", 1000) == 3   # skip_384's tail: the 1I1M goes
+    _, o = _check_case("many_ops", ref, rq, alns)
+    assert o["trace"].count("I") == 150 and o["trace"].count("D") == 150   # its gaps and insertions win their columns
+
+
+def test_full_house_of_300_base_subreads():
+    ids, grp = ccs_cases.full_house()
+    assert len(grp[0]) == ccseq.MAX_SUBREADS and all(len(s) == 300 for s in grp[0])
+    results, alns, _ = ccseq.run_groups([grp], device=False, threads=4)
+    assert sum(a is not None for a in alns[0]) == ccseq.MAX_SUBREADS - 1
+    o = _oracle(ccs_cases.zmw_case(ids, grp, alns[0]))
+    assert o["kept"] == "1" * (ccseq.MAX_SUBREADS - 1)   # every alignment is used
+    assert results[0][0] == 0 and _host_fastq(ids[grp[2]], results[0]) == o["fastq"] and results[0][3].decode() == o["trace"]
+
+
+# ---------------------------------------------------------------------------- chunks
+def test_chunk_batch_passes_one_launch():
+    """More groups, and more pairs, than one launch takes, and the groups around 65,535 differ."""
+    groups = ccs_cases.chunk_groups()
+    assert len(groups) == 65540 > 65535 and sum(len(g[0]) - 1 for g in groups) > 65535
+    assert all(len(s) == 60 for s in groups[65534][0]) and 60 > ccseq.default_params().min_aln_length
+    results, alns = ccs_cases.chunk_host()
+    edge = results[65533:65540]
+    assert len({r[1] for r in edge}) == 7 and all(r[0] == 0 and len(r[1]) >= 59 for r in edge)
+    assert all(ga[1] is None and ga[0] is not None and ga[0][0] == int(g % 3 == 2) for g, ga in enumerate(alns))
+    assert all(r[0] == 0 and r[1] for r in results)
 
 
 # ---------------------------------------------------------------------------- Perl goldens
