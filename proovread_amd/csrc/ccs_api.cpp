@@ -102,46 +102,6 @@ void map_group_host(const pr_ccs_params &p, const pr_ccs_batch *b, int g, pr_ccs
     }
 }
 
-void cns_group_host(const pr_ccs_params &p, const pr_ccs_batch *b, int g, const pr_ccs_alns *A, pr_ccs_out *O,
-                    std::vector<ColEnt> &slab) {
-    const int r = b->grp_ref[g];
-    const Read ref = read_of(b, r, 0);
-    const int L = ref.len;
-    std::vector<Read> reads;
-    std::vector<Prep> preps;
-    std::vector<AlnView> views;
-    O->seq_len[g] = O->trace_len[g] = 0;
-    for (int s = b->grp_off[g]; s < b->grp_off[g + 1]; ++s) {
-        if (s == r || !A->mapped[s]) continue;
-        const AlnView v = {read_of(b, s, A->strand[s] ? 1 : 0), A->pos[s], A->cigar + b->cig_off[s], A->n_cigar[s]};
-        const Prep pr = v.ncig > b->cig_off[s + 1] - b->cig_off[s] ? Prep{-1, 0, 0, 0, 0, 0, 0} : prep_aln(p, v, L);
-        if (pr.use < 0) {
-            O->status[g] = PR_CCS_BAD_ALN;
-            return;
-        }
-        if (pr.use == 1) reads.push_back(v.q), preps.push_back(pr), views.push_back(v);
-    }
-    const int m = (int)reads.size();
-    slab.assign((size_t)m * L, ColEnt{-1, -1, 0.0});
-    for (int a = 0; a < m; ++a) {
-        int rr = preps[a].rpos, q = 0;
-        for (int i = preps[a].cb; i < preps[a].ce; ++i) {
-            fill_op(p, views[a], preps[a], i, rr, q, slab.data() + (size_t)a * L);
-            advance_op(views[a], preps[a], i, rr, q);
-        }
-    }
-    uint8_t *seq = O->seq + b->out_off[g], *qual = O->qual + b->out_off[g], *trace = O->trace + b->out_off[g];
-    int ns = 0, nt = 0;
-    for (int c = 0; c < L; ++c) {
-        const Choice ch = decide_col(p, ref, c, slab.data(), L, m, reads.data());
-        int a = 0, t = 0;
-        choice_len(ch, slab.data(), L, c, a, t);
-        choice_emit(p, ch, ref, slab.data(), L, c, reads.data(), seq + ns, qual + ns, trace + nt);
-        ns += a, nt += t;
-    }
-    O->seq_len[g] = ns, O->trace_len[g] = nt;
-}
-
 int run_host(const pr_ccs_params &p, const pr_ccs_batch *b, int n_threads, pr_ccs_alns *A, bool do_map, pr_ccs_out *O) {
     over_groups(b->n_groups, n_threads, [&](int g) {
         const int st = group_status(b, g);

@@ -8,25 +8,18 @@
 //              over |(i - j) - d0| <= w with ksw_global2's cell (oracle/sw_oracle.c: gaps open
 //              from the diagonal value, M >= E >= F, extend only when strictly better than
 //              open), H floored at 0, first maximal cell in (i, j) order, traceback until H = 0
-//   consensus  Sam::Seq State_matrix / state_matrix_consensus (Seq.pm:232-467, 1568-1654) with
-//              Trim 1, InDelTaboo 0.001, use_ref_qual, qual_weighted: per alignment a column
-//              map (query offset, state length, weight); per column the six fixed states in
-//              registers and the insertion states compared as strings, sums in double in
-//              arrival order, ties between insertion states by global first-seen rank
+//   consensus  Sam::Seq State_matrix / state_matrix_consensus with Trim 1, InDelTaboo 0.001,
+//              use_ref_qual, qual_weighted: the rules are sm_core.h's; here an alignment is
+//              expanded into a column map (query offset, state length, weight per column, the
+//              slab), which is the source of the vote
 // The pieces marked CC_HD are the ones the kernels call.
 #pragma once
 #include <stdint.h>
 
 #include "../../include/prgpu.h"
-
-#if defined(__HIPCC__)
-#define CC_HD __host__ __device__ inline
-#else
-#define CC_HD inline
-#endif
+#include "sm_core.h"
 
 #include <algorithm>
-#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -34,19 +27,12 @@
 namespace prgpu {
 namespace ccs {
 
+using namespace sm;
+
 constexpr int NEG = -0x40000000;
 enum { DIR_SRC = 3, DIR_EEXT = 4, DIR_FEXT = 8, DIR_STOP = 16 };
-enum { OP_M = 0, OP_I = 1, OP_D = 2, OP_S = 4 };
 
-// a subread in an orientation: rev reads the reverse complement, qualities reversed
-struct Read {
-    const uint8_t *seq, *qual;
-    int32_t len, rev;
-};
 CC_HD int code_of(uint8_t c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4; }
-CC_HD uint8_t comp_of(uint8_t c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : 'N'; }
-CC_HD uint8_t base_at(const Read &r, int x) { return r.rev ? comp_of(r.seq[r.len - 1 - x]) : r.seq[x]; }
-CC_HD uint8_t qual_at(const Read &r, int x) { return r.rev ? r.qual[r.len - 1 - x] : r.qual[x]; }
 CC_HD int code_at(const Read &r, int x) { return code_of(base_at(r, x)); }
 // osw_fill_scmat: match a, mismatch -b, any N -1
 CC_HD int score_of(const pr_ccs_params &p, int r, int q) { return (r > 3 || q > 3) ? -1 : (r == q ? p.a : -p.b); }
@@ -308,102 +294,18 @@ inline Aln align_host(const pr_ccs_params &p, const Read &R, const Read &Q, int 
 }
 
 // ---------------------------------------------------------------------------
-// consensus
+// consensus: the State_matrix of sm_core.h over a slab of per-column entries
 
-// Seq.pm:151-156 Phreds2freqs, :136-142 Freqs2phreds
-CC_HD double phred2freq(int p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const double x = __dadd_rn(__dmul_rn(__ddiv_rn(__dmul_rn((double)p, (double)p), 120.0), 100.0), 0.5);
-    return __ddiv_rn((double)(long long)x, 100.0);
-#else
-    const double x = ((double)p * (double)p / 120.0) * 100.0 + 0.5;
-    return (double)(long long)x / 100.0;
-#endif
-}
-CC_HD int freq2phred(double f) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const double x = __dadd_rn(__dsqrt_rn(__dmul_rn(f, 120.0)), 0.5);
-#else
-    const double x = std::sqrt(f * 120.0) + 0.5;
-#endif
-    const long long p = (long long)x;
-    return p > 40 ? 40 : (int)p;
-}
-// Seq.pm:531-539: A T G C - N
-CC_HD int fixed_idx(uint8_t c) { return c == 'A' ? 0 : c == 'T' ? 1 : c == 'G' ? 2 : c == 'C' ? 3 : c == '-' ? 4 : 5; }
-CC_HD uint8_t fixed_chr(int idx) { return (uint8_t)("ATGC-N"[idx]); }
-
-struct AlnView {
-    Read q;   // in the aligned orientation
-    int32_t pos;
-    const uint32_t *cig;
-    int32_t ncig;
-};
-// what State_matrix keeps of an alignment: CIGAR ops [cb, ce), query window [wb, we), first column
-struct Prep {
-    int32_t use;   // 1 added, 0 skipped (Seq.pm:277, 354, 384), -1 malformed or leaving the reference
-    int32_t cb, ce, wb, we, rpos, lead;
-};
-// one state of an alignment in a reference column: the query bytes [qoff, qoff + slen) of the
-// aligned orientation; slen 0 a deletion, -1 no state; w its weight
-struct ColEnt {
-    int32_t qoff, slen;
-    double w;
-};
-
-// the trim of State_matrix (Seq.pm:316-385) over the ops [cb, ce) left after the clips were
-// stripped, query window [wb, we); taboo_len: InDelTabooLength, 0 for the InDelTaboo fraction
-CC_HD Prep prep_trim(const pr_ccs_params &p, const AlnView &a, int ref_len, int cb, int ce, int wb, int we, int taboo_len) {
-    Prep r = {0, 0, 0, 0, 0, 0, 0};
-    const int orig = a.q.len;
-    long rpos = a.pos;
-    if (p.trim) {
-        long mc = 0, dc = 0, ic = 0;
-        const long taboo = taboo_len ? (long)taboo_len : (long)((double)orig * p.indel_taboo + 0.5);
-        for (int i = cb; i < ce; ++i) {
-            const int op = (int)(a.cig[i] & 15);
-            const long n = (long)(a.cig[i] >> 4);
-            if (op == OP_M) {
-                if (mc + ic + n > taboo) {
-                    if (i > cb) cb = i, rpos += mc + dc, wb += (int)(mc + ic);
-                    break;
-                }
-                mc += n;
-            } else if (op == OP_D) {
-                dc += n;
-            } else {
-                ic += n;
-            }
-        }
-        if (we - wb < 50 || ((double)(we - wb) / (double)orig) < 0.7) return r;   // Seq.pm:354
-        long tail = 0;
-        for (int i = ce - 1; i != cb; --i) {   // never visits the first op
-            const int op = (int)(a.cig[i] & 15);
-            const long n = (long)(a.cig[i] >> 4);
-            if (op == OP_M) {
-                tail += n;
-                if (tail > taboo) {
-                    if (i < ce - 1) ce = i + 1, we -= (int)(tail - n);
-                    break;
-                }
-            } else if (op == OP_I) {
-                tail += n;
-            }
-        }
-        if (we - wb < p.min_aln_length || ((double)(we - wb) / (double)orig) < 0.7) return r;   // Seq.pm:384
-    }
-    r.cb = cb, r.ce = ce, r.wb = wb, r.we = we, r.rpos = (int32_t)rpos, r.lead = (a.cig[cb] & 15) == OP_I;
-    long cols = r.lead, q = 0;
-    for (int i = cb; i < ce; ++i) {
-        const int op = (int)(a.cig[i] & 15);
-        if (op != OP_I) cols += (long)(a.cig[i] >> 4);
-        if (op != OP_D) q += (long)(a.cig[i] >> 4);
-    }
-    r.use = (rpos < 0 || rpos + cols > ref_len || q != we - wb) ? -1 : 1;
-    return r;
+// ccseq's settings of Sam::Seq (ccseq:214-217): InDelTabooLength unset, MaxInsLength 0,
+// use_ref_qual and qual_weighted, one phred offset
+CC_HD Params sm_params(const pr_ccs_params &p) {
+    Params s = {};
+    s.trim = p.trim, s.min_aln_length = p.min_aln_length, s.phred_offset = s.ref_phred_offset = p.phred_offset;
+    s.indel_taboo = p.indel_taboo, s.use_ref_qual = s.qual_weighted = 1;
+    return s;
 }
 
-CC_HD Prep prep_aln(const pr_ccs_params &p, const AlnView &a, int ref_len) {
+CC_HD Prep prep_aln(const Params &p, const AlnView &a, int ref_len) {
     Prep r = {-1, 0, 0, 0, 0, 0, 0};
     const int orig = a.q.len;
     if (a.ncig <= 0) return r;
@@ -430,154 +332,83 @@ CC_HD Prep prep_aln(const pr_ccs_params &p, const AlnView &a, int ref_len) {
         r.use = -1;
         return r;
     }
-    return prep_trim(p, a, ref_len, cb, ce, wb, we, 0);
+    return prep_trim(p, a, ref_len, cb, ce, wb, we);
 }
 
-// min(Phreds2freqs(quals)) of the query bytes [qoff, qoff + n)
-CC_HD double state_weight(const pr_ccs_params &p, const Read &q, int qoff, int n) {
-    double m = 0.0;
-    for (int t = 0; t < n; ++t) {
-        const double f = phred2freq((int)qual_at(q, qoff + t) - p.phred_offset);
-        if (t == 0 || f < m) m = f;
-    }
-    return m;
-}
-// Seq.pm:402-408: the lesser of the qualities around a deletion at window position qpos
-CC_HD double del_weight(const pr_ccs_params &p, const Read &q, const Prep &pr, int qpos) {
-    const int n = pr.we - pr.wb;
-    const int xb = qpos > 1 ? qpos - 1 : qpos, xa = qpos < n ? qpos : qpos - 1;
-    const int qb = (xb >= 0 && xb < n) ? (int)qual_at(q, pr.wb + xb) : 0;
-    const int qa = (xa >= 0 && xa < n) ? (int)qual_at(q, pr.wb + xa) : 0;
-    const int c = qb < qa ? qb : qa;
-    return c ? phred2freq(c - p.phred_offset) : 0.0;
-}
-// the insertions that follow op i join the state before them (Seq.pm:412-424)
-CC_HD int ins_after(const AlnView &a, const Prep &pr, int i) {
-    int tot = 0;
-    for (int k = i + 1; k < pr.ce && (a.cig[k] & 15) == OP_I; ++k) tot += (int)(a.cig[k] >> 4);
-    return tot;
-}
-// the columns op i fills; r its first column, q its window position
-CC_HD void fill_op(const pr_ccs_params &p, const AlnView &a, const Prep &pr, int i, int r, int q, ColEnt *col) {
-    const int op = (int)(a.cig[i] & 15), n = (int)(a.cig[i] >> 4);
-    if (op == OP_I) {
-        if (i != pr.cb) return;
-        const int tot = n + ins_after(a, pr, i);   // a leading insertion is a state of its own column
-        col[r] = ColEnt{pr.wb + q, tot, state_weight(p, a.q, pr.wb + q, tot)};
-        return;
-    }
-    const int ins = ins_after(a, pr, i);
-    if (op == OP_M) {
-        for (int t = 0; t < n; ++t) {
-            const int sl = t == n - 1 ? 1 + ins : 1;
-            col[r + t] = ColEnt{pr.wb + q + t, sl, state_weight(p, a.q, pr.wb + q + t, sl)};
-        }
-        return;
-    }
-    const double wd = del_weight(p, a.q, pr, q);
-    for (int t = 0; t < n; ++t) col[r + t] = ColEnt{pr.wb + q, 0, wd};
-    if (ins) col[r + n - 1] = ColEnt{pr.wb + q, ins, state_weight(p, a.q, pr.wb + q, ins)};   // D+I: one replaced state
-}
-// first column / window position of the op after op i
-CC_HD void advance_op(const AlnView &a, const Prep &pr, int i, int &r, int &q) {
-    const int op = (int)(a.cig[i] & 15), n = (int)(a.cig[i] >> 4);
-    if (op != OP_I) r += n;
-    else if (i == pr.cb) r += 1;
-    if (op != OP_D) q += n;
+// op i expanded into the columns it covers (a leading insertion one, M and D their length; an
+// insertion behind another op is part of that op's last column); r its first column, q its
+// window position
+CC_HD void fill_op(const Params &p, const AlnView &a, const Prep &pr, int i, int r, int q, ColEnt *col) {
+    const bool ins = (a.cig[i] & 15) == OP_I;
+    if (ins && i != pr.cb) return;
+    const int n = ins ? 1 : (int)(a.cig[i] >> 4);
+    for (int t = 0; t < n; ++t) col[r + t] = entry_of_op(p, a, pr, i, r, q, r + t);
 }
 
-CC_HD bool same_state(const Read &x, int xo, const Read &y, int yo, int n) {
-    for (int t = 0; t < n; ++t)
-        if (base_at(x, xo + t) != base_at(y, yo + t)) return false;
-    return true;
-}
-// global rank of an insertion state: its first occurrence in (alignment, column) order
-CC_HD int64_t first_seen(const ColEnt *slab, int L, int m, const Read *reads, const Read &x, int xo, int n) {
-    for (int a = 0; a < m; ++a)
-        for (int c = 0; c < L; ++c) {
-            const ColEnt &e = slab[(size_t)a * L + c];
-            if (e.slen == n && same_state(reads[a], e.qoff, x, xo, n)) return (int64_t)a * L + c;
-        }
-    return -1;
-}
-
-// the consensus state of a column: kind 0 uncovered (the reference base), 1 a fixed state
-// (idx; 4 is the gap), 2 the state of alignment a at this column
-struct Choice {
-    int32_t kind, idx, a;
-    double f;
+// the vote's source: alignment k's entries for the L columns at slab[k * L]
+struct SlabSrc {
+    const ColEnt *slab;
+    int L, m;
+    const Read *reads;
+    CC_HD int count() const { return m; }
+    CC_HD ColEnt entry(int k, int c) const { return slab[(size_t)k * L + c]; }
+    CC_HD Read read(int k) const { return reads[k]; }
+    CC_HD bool ignored(int) const { return false; }
+    // the state's first occurrence among all entries in (alignment, column) order
+    CC_HD int64_t first_seen(const Read &x, int xo, int n) const {
+        for (int a = 0; a < m; ++a)
+            for (int c = 0; c < L; ++c) {
+                const ColEnt &e = slab[(size_t)a * L + c];
+                if (e.slen == n && same_state(reads[a], e.qoff, x, xo, n)) return (int64_t)a * L + c;
+            }
+        return -1;
+    }
 };
-CC_HD Choice decide_col(const pr_ccs_params &p, const Read &ref, int c, const ColEnt *slab, int L, int m, const Read *reads) {
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0, s5 = 0.0;
-    auto add = [&](int idx, double w) {
-        s0 += idx == 0 ? w : 0.0, s1 += idx == 1 ? w : 0.0, s2 += idx == 2 ? w : 0.0;
-        s3 += idx == 3 ? w : 0.0, s4 += idx == 4 ? w : 0.0, s5 += idx == 5 ? w : 0.0;
+
+// the host path of one group's consensus from the alignments in A; slab is the caller's scratch
+inline void cns_group_host(const pr_ccs_params &cp, const pr_ccs_batch *b, int g, const pr_ccs_alns *A, pr_ccs_out *O,
+                           std::vector<ColEnt> &slab) {
+    const Params p = sm_params(cp);
+    auto read_of = [&](int s, int rev) {
+        return Read{b->seq + b->off[s], b->qual + b->off[s], (int32_t)(b->off[s + 1] - b->off[s]), rev};
     };
-    const double fr = phred2freq((int)ref.qual[c] - p.phred_offset);
-    if (fr != 0.0) add(fixed_idx(ref.seq[c]), fr);
-    bool multi = false;
+    const int r = b->grp_ref[g];
+    const Read ref = read_of(r, 0);
+    const int L = ref.len;
+    std::vector<Read> reads;
+    std::vector<Prep> preps;
+    std::vector<AlnView> views;
+    O->seq_len[g] = O->trace_len[g] = 0;
+    for (int s = b->grp_off[g]; s < b->grp_off[g + 1]; ++s) {
+        if (s == r || !A->mapped[s]) continue;
+        const AlnView v = {read_of(s, A->strand[s] ? 1 : 0), A->pos[s], A->cigar + b->cig_off[s], A->n_cigar[s]};
+        const Prep pr = v.ncig > b->cig_off[s + 1] - b->cig_off[s] ? Prep{-1, 0, 0, 0, 0, 0, 0} : prep_aln(p, v, L);
+        if (pr.use < 0) {
+            O->status[g] = PR_CCS_BAD_ALN;
+            return;
+        }
+        if (pr.use == 1) reads.push_back(v.q), preps.push_back(pr), views.push_back(v);
+    }
+    const int m = (int)reads.size();
+    slab.assign((size_t)m * L, ColEnt{-1, -1, 0.0});
     for (int a = 0; a < m; ++a) {
-        const ColEnt &e = slab[(size_t)a * L + c];
-        if (e.slen == 0) add(4, e.w);
-        else if (e.slen == 1) add(fixed_idx(base_at(reads[a], e.qoff)), e.w);
-        else if (e.slen > 1) multi = true;
-    }
-    Choice ch = {0, 0, -1, 0.0};
-    const double s[6] = {s0, s1, s2, s3, s4, s5};
-    for (int i = 0; i < 6; ++i)
-        if (s[i] > ch.f) ch.f = s[i], ch.kind = 1, ch.idx = i;
-    if (!multi) return ch;
-    for (int a = 0; a < m; ++a) {
-        const ColEnt &e = slab[(size_t)a * L + c];
-        if (e.slen <= 1) continue;
-        bool seen = false;
-        for (int b = 0; b < a && !seen; ++b) {
-            const ColEnt &g = slab[(size_t)b * L + c];
-            seen = g.slen == e.slen && same_state(reads[b], g.qoff, reads[a], e.qoff, e.slen);
-        }
-        if (seen) continue;
-        double sum = 0.0;
-        for (int b = a; b < m; ++b) {
-            const ColEnt &g = slab[(size_t)b * L + c];
-            if (g.slen == e.slen && same_state(reads[b], g.qoff, reads[a], e.qoff, e.slen)) sum += g.w;
-        }
-        if (sum > ch.f) {
-            ch.f = sum, ch.kind = 2, ch.a = a;
-        } else if (sum == ch.f && sum > 0.0 && ch.kind == 2) {
-            // equal sums of two insertion states: the lower state index wins, the index is the
-            // rank of the state's first occurrence anywhere in the read (Seq.pm:441-443)
-            const ColEnt &g = slab[(size_t)ch.a * L + c];
-            if (first_seen(slab, L, m, reads, reads[a], e.qoff, e.slen) <
-                first_seen(slab, L, m, reads, reads[ch.a], g.qoff, g.slen))
-                ch.a = a;
+        int rr = preps[a].rpos, q = 0;
+        for (int i = preps[a].cb; i < preps[a].ce; ++i) {
+            fill_op(p, views[a], preps[a], i, rr, q, slab.data() + (size_t)a * L);
+            advance_op(views[a], preps[a], i, rr, q);
         }
     }
-    return ch;
-}
-// bases and trace characters a column emits (Seq.pm:1620-1650)
-CC_HD void choice_len(const Choice &ch, const ColEnt *slab, int L, int c, int &nseq, int &ntrace) {
-    if (ch.kind == 1 && ch.idx == 4) nseq = 0, ntrace = 1;
-    else if (ch.kind == 2) nseq = ntrace = slab[(size_t)ch.a * L + c].slen;
-    else nseq = ntrace = 1;
-}
-CC_HD void choice_emit(const pr_ccs_params &p, const Choice &ch, const Read &ref, const ColEnt *slab, int L, int c,
-                       const Read *reads, uint8_t *seq, uint8_t *qual, uint8_t *trace) {
-    if (ch.kind == 1 && ch.idx == 4) {
-        trace[0] = 'I';
-        return;
+    const SlabSrc src = {slab.data(), L, m, reads.data()};
+    uint8_t *seq = O->seq + b->out_off[g], *qual = O->qual + b->out_off[g], *trace = O->trace + b->out_off[g];
+    int ns = 0, nt = 0;
+    for (int c = 0; c < L; ++c) {
+        const Pick pk = decide_col(p, ref, c, src);
+        int a = 0, t = 0;
+        pick_len(pk, a, t);
+        pick_emit(p, pk, ref, c, src, seq + ns, qual + ns, trace + nt);
+        ns += a, nt += t;
     }
-    const uint8_t ph = (uint8_t)(freq2phred(ch.f) + p.phred_offset);
-    trace[0] = 'M';
-    if (ch.kind == 2) {
-        const ColEnt &e = slab[(size_t)ch.a * L + c];
-        for (int t = 0; t < e.slen; ++t) {
-            seq[t] = base_at(reads[ch.a], e.qoff + t), qual[t] = ph;
-            if (t) trace[t] = 'D';
-        }
-    } else {
-        seq[0] = ch.kind == 1 ? fixed_chr(ch.idx) : ref.seq[c];
-        qual[0] = ph;
-    }
+    O->seq_len[g] = ns, O->trace_len[g] = nt;
 }
 
 }   // namespace ccs

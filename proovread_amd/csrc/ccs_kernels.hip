@@ -19,6 +19,7 @@
 //                      written out through a block prefix sum.
 #include <hip/hip_runtime.h>
 
+#include "block_scan.h"
 #include "ccs_dev.h"
 
 namespace prgpu {
@@ -208,7 +209,7 @@ __global__ __launch_bounds__(CNS_BLOCK) void ccs_cns_kernel(CcsDev D, CcsCnsDev 
     __shared__ int32_t scan_a[CNS_BLOCK], scan_b[CNS_BLOCK];
     __shared__ int32_t m_sh, bad_sh;
     const int g = C.glist[blockIdx.x], tid = threadIdx.x;
-    const pr_ccs_params p = D.p;
+    const Params p = sm_params(D.p);
     const int s0 = D.grp_off[g], ns = D.grp_off[g + 1] - s0, r = D.grp_ref[g];
     const Read ref = read_of(D, r, 0);
     const int L = ref.len;
@@ -263,26 +264,20 @@ __global__ __launch_bounds__(CNS_BLOCK) void ccs_cns_kernel(CcsDev D, CcsCnsDev 
     __threadfence_block();
     __syncthreads();
     const int64_t ob = C.out_off[g], cap = C.out_off[g + 1] - ob;
+    const SlabSrc src = {slab, L, m, reads};
     int seq_base = 0, trace_base = 0;
     for (int base = 0; base < L; base += CNS_BLOCK) {
         const int c = base + tid;
-        Choice ch = {0, 0, -1, 0.0};
+        Pick pk = {0, 0, -1, 0.0, 0, 0};
         int nseq = 0, ntrace = 0;
         if (c < L) {
-            ch = decide_col(p, ref, c, slab, L, m, reads);
-            choice_len(ch, slab, L, c, nseq, ntrace);
+            pk = decide_col(p, ref, c, src);
+            pick_len(pk, nseq, ntrace);
         }
-        scan_a[tid] = nseq, scan_b[tid] = ntrace;
-        __syncthreads();
-        for (int st = 1; st < CNS_BLOCK; st <<= 1) {
-            const int xa = tid >= st ? scan_a[tid - st] : 0, xb = tid >= st ? scan_b[tid - st] : 0;
-            __syncthreads();
-            scan_a[tid] += xa, scan_b[tid] += xb;
-            __syncthreads();
-        }
-        const int so = seq_base + scan_a[tid] - nseq, to = trace_base + scan_b[tid] - ntrace;
+        const int so = seq_base + block_scan<CNS_BLOCK>(nseq, scan_a) - nseq;
+        const int to = trace_base + block_scan<CNS_BLOCK>(ntrace, scan_b) - ntrace;
         if (c < L && so + nseq <= cap && to + ntrace <= cap)
-            choice_emit(p, ch, ref, slab, L, c, reads, C.seq + ob + so, C.qual + ob + so, C.trace + ob + to);
+            pick_emit(p, pk, ref, c, src, C.seq + ob + so, C.qual + ob + so, C.trace + ob + to);
         seq_base += scan_a[CNS_BLOCK - 1], trace_base += scan_b[CNS_BLOCK - 1];
         __syncthreads();
     }

@@ -78,7 +78,7 @@ int run_host(const pr_utg_params &p, const pr_utg_batch *b, int n_threads, pr_ut
     std::vector<double> sc(na);
     std::vector<uint8_t> flag(na);
     View V = {};
-    V.p = p, V.cp = cns_params(p), V.b = *b, V.o = *o;
+    V.p = p, V.sp = sm_params(p), V.b = *b, V.o = *o;
     V.b.qual = qual.data();
     V.prep = prep.data(), V.alen = alen.data(), V.span_e = span_e.data(), V.sc = sc.data(), V.flag = flag.data();
     V.op_r = op_r.data(), V.op_q = op_q.data(), V.cov = cov.data(), V.ulist = ulist.data(), V.rlist = rlist.data();
@@ -172,7 +172,7 @@ int run_gpu(pr_ctx *c, const pr_utg_params &p, const pr_utg_batch *b, pr_utg_out
         HIPCHK(hipMemsetAsync(buf[B_OKEPT].p, 0, (size_t)na + 1, s));
         if ((e = buf[B_OWIN].ensure((size_t)(2 * nwin) * sizeof(int32_t)))) return e;
         View V = {};
-        V.p = p, V.cp = cns_params(p);
+        V.p = p, V.sp = sm_params(p);
         V.b = *b;
         V.b.read_off = buf[B_ROFF].as<int64_t>(), V.b.ref_seq = buf[B_RSEQ].as<uint8_t>();
         V.b.ref_qual = b->ref_qual ? buf[B_RQUAL].as<uint8_t>() : nullptr;

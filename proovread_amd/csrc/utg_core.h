@@ -10,25 +10,23 @@
 //
 // The map from (alignment, column) to a state is never stored: every CIGAR op keeps its first
 // column and its first query position (op_r, op_q), a column finds its op by bisection and the
-// state and its weight follow from the op (entry_at).  Memory grows with the ops, not the spans.
-// The pieces of ccs_core.h do the arithmetic: prep_trim, state_weight, del_weight, ins_after,
-// same_state, phred2freq, freq2phred.  The pieces marked CC_HD are the ones the kernels call.
+// state and its weight follow from the op (OpSrc).  Memory grows with the ops, not the spans.
+// The trim, the states and the vote of step 5 are sm_core.h's; OpSrc is the vote's source here.
+// The pieces marked CC_HD are the ones the kernels call.
 #pragma once
-#include "ccs_core.h"
+#include <stdint.h>
+
+#include "../../include/prgpu.h"
+#include "sm_core.h"
+
+#include <algorithm>
+#include <vector>
 
 namespace prgpu {
 namespace utg {
 
-using ccs::AlnView;
-using ccs::Choice;
-using ccs::ColEnt;
-using ccs::OP_D;
-using ccs::OP_I;
-using ccs::OP_M;
-using ccs::OP_S;
-using ccs::Prep;
-using ccs::Read;
-enum { OP_H = 5 };
+using namespace sm;
+
 // per alignment: alive after step 1, after step 2, after step 3; ncscore of a length 0
 enum { F_ALIVE1 = 1, F_ALIVE2 = 2, F_KEPT = 4, F_DIV0 = 8 };
 constexpr int FILTER_LDS = 2048;   // alignments of a read the contained filter sorts on chip
@@ -37,7 +35,7 @@ constexpr int FILTER_LDS = 2048;   // alignments of a read the contained filter 
 // every pointer is valid where the code runs
 struct View {
     pr_utg_params p;
-    pr_ccs_params cp;         // the settings ccs_core.h's pieces read
+    Params sp;                // what sm_core.h's pieces read of p
     pr_utg_batch b;
     pr_utg_out o;
     const int32_t *aln_read;  // [n_alns] the read of an alignment
@@ -54,10 +52,12 @@ struct View {
     double *f_sc;
 };
 
-CC_HD pr_ccs_params cns_params(const pr_utg_params &p) {
-    pr_ccs_params c = {};
-    c.trim = p.trim, c.min_aln_length = p.min_aln_length, c.phred_offset = p.phred_offset, c.indel_taboo = p.indel_taboo;
-    return c;
+CC_HD Params sm_params(const pr_utg_params &p) {
+    Params s = {};
+    s.trim = p.trim, s.min_aln_length = p.min_aln_length, s.phred_offset = p.phred_offset, s.ref_phred_offset = p.ref_phred_offset;
+    s.indel_taboo = p.indel_taboo, s.indel_taboo_length = p.indel_taboo_length;
+    s.use_ref_qual = p.use_ref_qual, s.qual_weighted = p.qual_weighted, s.max_ins_length = p.max_ins_length;
+    return s;
 }
 CC_HD double ddiv(double a, double b) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -106,7 +106,7 @@ CC_HD Prep prep_utg(const View &V, const AlnView &a, int ref_len) {
         else if (op(i) != OP_D) return bad;   // "Unknown Cigar"
     }
     if (we < wb || qsum != we - wb) return bad;
-    return ccs::prep_trim(V.cp, a, ref_len, cb, ce, (int)wb, (int)we, V.p.indel_taboo_length);
+    return prep_trim(V.sp, a, ref_len, cb, ce, (int)wb, (int)we);
 }
 
 // Alignment.pm:417-431
@@ -128,7 +128,7 @@ CC_HD void prep_one(const View &V, int64_t a, int ref_len) {
     if (pr.use == 1)
         for (int i = pr.cb; i < pr.ce; ++i) {
             V.op_r[V.b.cig_off[a] + i] = r, V.op_q[V.b.cig_off[a] + i] = q;
-            ccs::advance_op(v, pr, i, r, q);
+            advance_op(v, pr, i, r, q);
         }
     V.span_e[a] = r;
     const long len = aln_length(v);
@@ -207,23 +207,6 @@ CC_HD bool ignored(const View &V, int r, int c) {
     return false;
 }
 
-// the state op i gives column c: query bytes [qoff, qoff + slen), slen 0 a deletion
-// (Seq.pm:396-432; a leading insertion is a column of its own, D+I one replaced state)
-CC_HD ColEnt state_of_op(const AlnView &a, const Prep &pr, int i, int r, int q, int c) {
-    const int op = (int)(a.cig[i] & 15), n = (int)(a.cig[i] >> 4);
-    if (op == OP_I) return ColEnt{pr.wb + q, n + ccs::ins_after(a, pr, i), 0.0};
-    const int ins = c - r == n - 1 ? ccs::ins_after(a, pr, i) : 0;
-    if (op == OP_M) return ColEnt{pr.wb + q + (c - r), 1 + ins, 0.0};
-    return ColEnt{pr.wb + q, ins, 0.0};
-}
-// ... with its weight: min(Phreds2freqs) or 1 (Seq.pm:450-459)
-CC_HD ColEnt entry_of_op(const View &V, const AlnView &a, const Prep &pr, int i, int r, int q, int c) {
-    ColEnt e = state_of_op(a, pr, i, r, q, c);
-    if (!V.p.qual_weighted) e.w = 1.0;
-    else if (e.slen > 0) e.w = ccs::state_weight(V.cp, a.q, e.qoff, e.slen);
-    else e.w = ccs::del_weight(V.cp, a.q, pr, q);
-    return e;
-}
 // the op of column c: the last one that starts at or before it (an insertion behind another op
 // starts where the next op does and is never the last)
 CC_HD int op_of_col(const Prep &pr, const int32_t *opr, int c) {
@@ -235,123 +218,47 @@ CC_HD int op_of_col(const Prep &pr, const int32_t *opr, int c) {
     }
     return lo - 1;
 }
-CC_HD ColEnt entry_at(const View &V, int64_t a, const AlnView &v, const Prep &pr, int c) {
-    const int32_t *opr = V.op_r + V.b.cig_off[a], *opq = V.op_q + V.b.cig_off[a];
-    const int i = op_of_col(pr, opr, c);
-    return entry_of_op(V, v, pr, i, opr[i], opq[i], c);
-}
 
-// rank of an insertion state (Seq.pm:446-448): its first occurrence over the alignments of
-// rlist in (alignment, column) order; ign: the pass that ranks skips ignored columns
-CC_HD int64_t first_seen(const View &V, int r, const int32_t *rlist, int m, bool ign, const Read &x, int xo, int n) {
-    for (int k = 0; k < m; ++k) {
-        const int64_t a = rlist[k];
-        const AlnView v = view_of(V.b, a);
-        const Prep pr = V.prep[a];
-        const int32_t *opr = V.op_r + V.b.cig_off[a], *opq = V.op_q + V.b.cig_off[a];
-        for (int i = pr.cb; i < pr.ce; ++i) {
-            const int op = (int)(v.cig[i] & 15);
-            if (op == OP_I && i != pr.cb) continue;
-            const int c = op == OP_I ? opr[i] : opr[i] + (int)(v.cig[i] >> 4) - 1;
-            const ColEnt e = state_of_op(v, pr, i, opr[i], opq[i], c);
-            if (e.slen != n || !ccs::same_state(v.q, e.qoff, x, xo, n)) continue;
-            if (ign && ignored(V, r, c)) continue;
-            return (int64_t)k << 32 | (int64_t)c;
-        }
-    }
-    return INT64_MAX;
-}
-
-// the consensus state of column c over the alignments lst[0, m) (arrival order; those that do
-// not span c are passed over): ccs::Choice with a the alignment, and the state's bytes
-struct Pick {
-    Choice ch;
-    int32_t qoff, slen;
-};
-CC_HD Pick decide_col(const View &V, int r, const Read &ref, int c, const int32_t *lst, int m) {
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0, s5 = 0.0;
-    auto add = [&](int idx, double w) {
-        s0 += idx == 0 ? w : 0.0, s1 += idx == 1 ? w : 0.0, s2 += idx == 2 ? w : 0.0;
-        s3 += idx == 3 ? w : 0.0, s4 += idx == 4 ? w : 0.0, s5 += idx == 5 ? w : 0.0;
-    };
-    if (V.p.use_ref_qual && ref.qual) {   // Seq.pm:256-266
-        const double fr = ccs::phred2freq((int)ref.qual[c] - V.p.ref_phred_offset);
-        if (fr != 0.0) add(ccs::fixed_idx(ref.seq[c]), fr);
-    }
-    const bool ign = ignored(V, r, c);
-    const int max_ins = V.p.max_ins_length;
-    bool multi = false;
-    auto covers = [&](int64_t a) { return c >= V.prep[a].rpos && c < V.span_e[a]; };
-    if (!ign)
-        for (int k = 0; k < m; ++k) {
-            const int64_t a = lst[k];
-            if (!covers(a)) continue;
-            const AlnView v = view_of(V.b, a);
-            const ColEnt e = entry_at(V, a, v, V.prep[a], c);
-            if (e.slen == 0) add(4, e.w);
-            else if (e.slen == 1) add(ccs::fixed_idx(v.q.seq[e.qoff]), e.w);
-            else multi = true;
-        }
-    Pick pk = {{0, 0, -1, 0.0}, 0, 0};
-    const double s[6] = {s0, s1, s2, s3, s4, s5};
-    for (int i = 0; i < 6; ++i)
-        if (s[i] > pk.ch.f) pk.ch.f = s[i], pk.ch.kind = 1, pk.ch.idx = i;
-    if (!multi) return pk;
-    for (int k = 0; k < m; ++k) {
+// the vote's source: the alignments lst[0, m) of read r in arrival order; a column finds its op
+// in each by bisection, an alignment that does not span the column has no state there
+struct OpSrc {
+    const View &V;
+    int r;
+    const int32_t *lst;
+    int m;
+    CC_HD int count() const { return m; }
+    CC_HD Read read(int k) const { return view_of(V.b, lst[k]).q; }
+    CC_HD bool ignored(int c) const { return utg::ignored(V, r, c); }
+    CC_HD ColEnt entry(int k, int c) const {
         const int64_t a = lst[k];
-        if (!covers(a)) continue;
-        const AlnView va = view_of(V.b, a);
-        const ColEnt e = entry_at(V, a, va, V.prep[a], c);
-        if (e.slen <= 1 || (max_ins && e.slen > max_ins)) continue;   // Seq.pm:1607
-        bool seen = false;
-        double sum = 0.0;
-        for (int j = 0; j < m && !seen; ++j) {
-            const int64_t b = lst[j];
-            if (!covers(b)) continue;
-            const AlnView vb = view_of(V.b, b);
-            const ColEnt g = entry_at(V, b, vb, V.prep[b], c);
-            if (g.slen != e.slen || !ccs::same_state(vb.q, g.qoff, va.q, e.qoff, e.slen)) continue;
-            if (j < k) seen = true;
-            else sum += g.w;
-        }
-        if (seen) continue;
-        if (sum > pk.ch.f) {
-            pk.ch.f = sum, pk.ch.kind = 2, pk.ch.a = (int32_t)a, pk.qoff = e.qoff, pk.slen = e.slen;
-        } else if (sum == pk.ch.f && sum > 0.0 && pk.ch.kind == 2) {
-            // equal sums of two insertion states: the lower state index wins (Seq.pm:1593-1611)
-            const int32_t *rl = V.rlist + V.b.aln_off[r];
-            const bool rign = !V.p.has_rep_coverage;
-            const AlnView vw = view_of(V.b, pk.ch.a);
-            if (first_seen(V, r, rl, V.n_r[r], rign, va.q, e.qoff, e.slen) < first_seen(V, r, rl, V.n_r[r], rign, vw.q, pk.qoff, pk.slen))
-                pk.ch.a = (int32_t)a, pk.qoff = e.qoff, pk.slen = e.slen;
-        }
+        if (c < V.prep[a].rpos || c >= V.span_e[a]) return ColEnt{0, -1, 0.0};
+        const int32_t *opr = V.op_r + V.b.cig_off[a], *opq = V.op_q + V.b.cig_off[a];
+        const int i = op_of_col(V.prep[a], opr, c);
+        return entry_of_op(V.sp, view_of(V.b, a), V.prep[a], i, opr[i], opq[i], c);
     }
-    return pk;
-}
-// bases and trace characters a column emits (Seq.pm:1616-1635)
-CC_HD void pick_len(const Pick &pk, int &nseq, int &ntrace) {
-    if (pk.ch.kind == 1 && pk.ch.idx == 4) nseq = 0, ntrace = 1;
-    else if (pk.ch.kind == 2) nseq = ntrace = pk.slen;
-    else nseq = ntrace = 1;
-}
-CC_HD void pick_emit(const View &V, const Pick &pk, const Read &ref, int c, uint8_t *seq, uint8_t *qual, uint8_t *trace) {
-    if (pk.ch.kind == 1 && pk.ch.idx == 4) {
-        trace[0] = 'I';
-        return;
-    }
-    const uint8_t ph = (uint8_t)(ccs::freq2phred(pk.ch.f) + V.p.phred_offset);
-    trace[0] = 'M';
-    if (pk.ch.kind == 2) {
-        const uint8_t *q = V.b.seq + V.b.seq_off[pk.ch.a];
-        for (int t = 0; t < pk.slen; ++t) {
-            seq[t] = q[pk.qoff + t], qual[t] = ph;
-            if (t) trace[t] = 'D';
+    // Seq.pm:446-448: the state's first occurrence over the alignments of rlist (step 2's matrix
+    // when it ran, which had no ignored columns) in (alignment, column) order
+    CC_HD int64_t first_seen(const Read &x, int xo, int n) const {
+        const int32_t *rlist = V.rlist + V.b.aln_off[r];
+        const bool ign = !V.p.has_rep_coverage;
+        for (int k = 0; k < V.n_r[r]; ++k) {
+            const int64_t a = rlist[k];
+            const AlnView v = view_of(V.b, a);
+            const Prep pr = V.prep[a];
+            const int32_t *opr = V.op_r + V.b.cig_off[a], *opq = V.op_q + V.b.cig_off[a];
+            for (int i = pr.cb; i < pr.ce; ++i) {
+                const int op = (int)(v.cig[i] & 15);
+                if (op == OP_I && i != pr.cb) continue;
+                const int c = op == OP_I ? opr[i] : opr[i] + (int)(v.cig[i] >> 4) - 1;
+                const ColEnt e = state_of_op(v, pr, i, opr[i], opq[i], c);
+                if (e.slen != n || !same_state(v.q, e.qoff, x, xo, n)) continue;
+                if (ign && utg::ignored(V, r, c)) continue;
+                return (int64_t)k << 32 | (int64_t)c;
+            }
         }
-    } else {
-        seq[0] = pk.ch.kind == 1 ? ccs::fixed_chr(pk.ch.idx) : ref.seq[c];
-        qual[0] = ph;
+        return INT64_MAX;
     }
-}
+};
 
 // which alignments a State_matrix pass parses: those of the ranks (step 2's matrix when it ran)
 // and those of the consensus; a malformed one among them is the read's PR_UTG_BAD_ALN
@@ -444,10 +351,11 @@ inline void run_read_host(const View &V, int r) {
         const size_t before = live.size();
         live.erase(std::remove_if(live.begin(), live.end(), [&](int32_t a) { return V.span_e[a] <= c; }), live.end());
         if (changed || before != live.size()) std::sort(live.begin(), live.end());   // arrival order
-        const Pick pk = decide_col(V, r, ref, c, live.data(), (int)live.size());
+        const OpSrc src = {V, r, live.data(), (int)live.size()};
+        const Pick pk = decide_col(V.sp, ref, c, src);
         int a = 0, t = 0;
         pick_len(pk, a, t);
-        pick_emit(V, pk, ref, c, seq + ns, qual + ns, trace + nt);
+        pick_emit(V.sp, pk, ref, c, src, seq + ns, qual + ns, trace + nt);
         ns += a, nt += t;
     }
     V.o.seq_len[r] = ns, V.o.trace_len[r] = nt;

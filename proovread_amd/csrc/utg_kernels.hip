@@ -17,6 +17,7 @@
 // Integer atomics only (the difference array); all stores are plain vector stores.
 #include <hip/hip_runtime.h>
 
+#include "block_scan.h"
 #include "utg_dev.h"
 
 namespace prgpu {
@@ -27,21 +28,6 @@ namespace {
 
 constexpr int BLK = 256;
 constexpr int TILE_CAP = 1024;   // alignments a tile lists in LDS; more: the columns walk the read's list
-
-// inclusive prefix sum over the block; sh[BLK - 1] holds the total until the next call
-__device__ inline int block_scan(int v, int *sh) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    sh[tid] = v;
-    __syncthreads();
-    for (int st = 1; st < BLK; st <<= 1) {
-        const int x = tid >= st ? sh[tid - st] : 0;
-        __syncthreads();
-        sh[tid] += x;
-        __syncthreads();
-    }
-    return sh[tid];
-}
 
 __global__ __launch_bounds__(BLK) void utg_prep_kernel(View V) {
     const int64_t a = (int64_t)blockIdx.x * BLK + threadIdx.x;
@@ -97,7 +83,7 @@ __global__ __launch_bounds__(BLK) void utg_cov_kernel(View V) {
     // column L closes a run that reaches the end (bam2cns:421)
     for (int base = 0; base <= L; base += BLK) {
         const int c = base + tid;
-        const int cv = carry + block_scan(c < L ? cov[c] : 0, sh);
+        const int cv = carry + block_scan<BLK>(c < L ? cov[c] : 0, sh);
         const int total = sh[BLK - 1];
         const int h = c < L && !(cv < V.p.rep_coverage);
         hs[tid] = h;
@@ -105,7 +91,7 @@ __global__ __launch_bounds__(BLK) void utg_cov_kernel(View V) {
         const int prev = tid ? hs[tid - 1] : prev_high;
         const int last = hs[BLK - 1];
         const int st = h && !prev, en = !h && prev && c <= L;
-        const int si = nw + block_scan(st, sh);   // starts up to and with this column
+        const int si = nw + block_scan<BLK>(st, sh);   // starts up to and with this column
         const int nst = sh[BLK - 1];
         if (st && si - 1 < wcap) win[2 * (si - 1)] = c;
         if (en && si - 1 < wcap) win[2 * (si - 1) + 1] = c;
@@ -197,7 +183,7 @@ __global__ __launch_bounds__(BLK) void utg_cns_kernel(View V) {
             bad |= kept && use < 0;
             u = kept && use == 1, rk = in_rank_pass(V, a) && use == 1;
         }
-        const int ui = nu + block_scan(u, sh_a), ri = nr + block_scan(rk, sh_b);
+        const int ui = nu + block_scan<BLK>(u, sh_a), ri = nr + block_scan<BLK>(rk, sh_b);
         if (u) ulist[ui - 1] = (int32_t)a;
         if (rk) rlist[ri - 1] = (int32_t)a;
         nu += sh_a[BLK - 1], nr += sh_b[BLK - 1];
@@ -220,23 +206,22 @@ __global__ __launch_bounds__(BLK) void utg_cns_kernel(View V) {
             const int k = kb + tid;
             const int32_t a = k < nu ? ulist[k] : -1;
             const int ov = a >= 0 && V.prep[a].rpos < base + BLK && V.span_e[a] > base;
-            const int at = mt + block_scan(ov, sh_a);
+            const int at = mt + block_scan<BLK>(ov, sh_a);
             if (ov && at - 1 < TILE_CAP) tile[at - 1] = a;
             mt += sh_a[BLK - 1];
         }
         __syncthreads();
-        const int32_t *lst = mt <= TILE_CAP ? tile : ulist;
-        const int m = mt <= TILE_CAP ? mt : nu;
+        const OpSrc src = {V, r, mt <= TILE_CAP ? tile : ulist, mt <= TILE_CAP ? mt : nu};
         const int c = base + tid;
-        Pick pk = {{0, 0, -1, 0.0}, 0, 0};
+        Pick pk = {0, 0, -1, 0.0, 0, 0};
         int nseq = 0, ntrace = 0;
         if (c < L) {
-            pk = decide_col(V, r, ref, c, lst, m);
+            pk = decide_col(V.sp, ref, c, src);
             pick_len(pk, nseq, ntrace);
         }
-        const int so = seq_base + block_scan(nseq, sh_a) - nseq, to = trace_base + block_scan(ntrace, sh_b) - ntrace;
+        const int so = seq_base + block_scan<BLK>(nseq, sh_a) - nseq, to = trace_base + block_scan<BLK>(ntrace, sh_b) - ntrace;
         if (c < L && so + nseq <= cap && to + ntrace <= cap)
-            pick_emit(V, pk, ref, c, V.o.seq + ob + so, V.o.qual + ob + so, V.o.trace + ob + to);
+            pick_emit(V.sp, pk, ref, c, src, V.o.seq + ob + so, V.o.qual + ob + so, V.o.trace + ob + to);
         seq_base += sh_a[BLK - 1], trace_base += sh_b[BLK - 1];
         __syncthreads();
     }

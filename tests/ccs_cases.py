@@ -1,7 +1,8 @@
 """Groups and alignments the ccs consensus tests share — TEST INFRASTRUCTURE.
 
 A case is a reference subread plus alignments given as (SEQ, QUAL, pos0, CIGAR) in arrival
-order: hand-made ones that reach the corners of Sam::Seq's State_matrix under ccseq's settings,
+order, SEQ and QUAL in the aligned orientation; a fifth element 1 marks a subread sequenced from
+the other strand: hand-made ones that reach the corners of Sam::Seq's State_matrix under ccseq's settings,
 and helpers that turn a case into the library's hook input and into a casefmt.Case for the
 oracle and the Perl goldens.
 
@@ -53,7 +54,8 @@ def q(n, c="?"):
     return c * n
 
 
-HAND_NAMES = ["ins_tie_rank", "skip_277", "skip_354", "skip_384", "del_ins_pair", "leading_ins", "del_quals", "ref_alone"]
+HAND_NAMES = ["ins_tie_rank", "skip_277", "skip_354", "skip_384", "del_ins_pair", "leading_ins", "del_quals", "ref_alone",
+              "rev_ins_wins"]
 
 
 def hand_cases():
@@ -115,13 +117,25 @@ def hand_cases():
     # the reference alone: no alignment is usable; columns of weight 0 (quality '!') are uncovered
     rq = "".join("!" if k % 7 == 0 else "5" for k in range(130))
     cases["ref_alone"] = (ref, rq, [(short, q(50, "I"), 20, "50M")])
+
+    # column 40 holds two insertion states of three bases: the first alignment, from the reverse
+    # strand (phred 33-47: weight >= 9.08), and the second (2-16: <= 2.13) carry one, the third
+    # (17-31: 2.41 to 8.01) the other.  The second alone loses to the third; with the first it
+    # wins, so the winning state is compared and written through the reverse strand's subread
+    ref = rand_seq(rng, 80)
+    ramp = lambda n, lo: "".join(chr(33 + lo + (7 * k) % 15) for k in range(n))   # noqa: E731
+    r1 = query_of(ref, 1, "40M2I37M", rng, ["GT"])
+    f2 = query_of(ref, 0, "41M2I35M", rng, ["GT"])
+    f3 = query_of(ref, 3, "38M2I39M", rng, ["CC"])
+    cases["rev_ins_wins"] = (ref, q(80, "#"), [(r1, ramp(len(r1), 33), 1, "40M2I37M", 1), (f2, ramp(len(f2), 2), 0, "41M2I35M"),
+                                               (f3, ramp(len(f3), 17), 3, "38M2I39M")])
     return cases
 
 
 def to_case(name: str, ref: str, rq: str, alns: List[Aln]) -> casefmt.Case:
     rid = f"m1/{len(name)}/0_{len(ref)}"
-    sam = ["\t".join([f"q{k}", "0", rid, str(pos + 1), "60", cig, "*", "0", "0", s, ql, "AS:i:100"])
-           for k, (s, ql, pos, cig) in enumerate(alns)]
+    sam = ["\t".join([f"q{k}", "16" if a[4:] == (1,) else "0", rid, str(a[2] + 1), "60", a[3], "*", "0", "0", a[0], a[1], "AS:i:100"])
+           for k, a in enumerate(alns)]
     return casefmt.Case(name, {"qual_weighted": "1", "use_ref_qual": "1"}, ["@" + rid, ref, "+", rq], sam)
 
 
@@ -135,9 +149,10 @@ def case_alns(case: casefmt.Case) -> List[Aln]:
 
 def to_group(ref: str, rq: str, alns: List[Aln]):
     """-> (Group, alignments) for ccseq.consensus_groups: the reference is subread 0, every
-    alignment a forward subread."""
-    grp = ([ref.encode()] + [a[0].encode() for a in alns], [rq.encode("latin-1")] + [a[1].encode("latin-1") for a in alns], 0)
-    return grp, [None] + [(0, a[2], 100, a[3]) for a in alns]
+    alignment a subread, stored as sequenced."""
+    sub = [(ccs_ref.revcomp(a[0]), a[1][::-1]) if a[4:] == (1,) else (a[0], a[1]) for a in alns]
+    grp = ([ref.encode()] + [s.encode() for s, _ in sub], [rq.encode("latin-1")] + [ql.encode("latin-1") for _, ql in sub], 0)
+    return grp, [None] + [(int(a[4:] == (1,)), a[2], 100, a[3]) for a in alns]
 
 
 ORACLE_OVER = dict(max_coverage=1e9, indel_taboo_length=0, indel_taboo=0.001, qual_weighted=1)

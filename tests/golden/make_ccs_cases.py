@@ -17,7 +17,8 @@ from proovread_amd import ccseq  # noqa: E402
 
 
 def main(out):
-    cases = [ccs_cases.to_case(name, *c) for name, c in ccs_cases.hand_cases().items()]
+    # rev_ins_wins came after the Perl records were written; the C oracle holds it
+    cases = [ccs_cases.to_case(name, *c) for name, c in ccs_cases.hand_cases().items() if name != "rev_ins_wins"]
     rng = random.Random(31)
     for z, w in enumerate((8, 300, 8, 300)):
         _, recs = ccs_ref.sim_zmw(rng, "m150101_1_s1_p0", 100 + z, rng.randrange(150, 260), rng.randrange(3, 7))

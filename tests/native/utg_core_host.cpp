@@ -5,6 +5,7 @@
 // the golden file.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <iostream>
 #include <sstream>
@@ -113,7 +114,7 @@ void run_case(const Case &c) {
     std::vector<double> sc((size_t)na);
     std::vector<uint8_t> flag((size_t)na);
     View V = {};
-    V.p = p, V.cp = cns_params(p);
+    V.p = p, V.sp = sm_params(p);
     V.b.n_reads = 1, V.b.n_alns = na, V.b.read_off = read_off, V.b.ref_seq = (const uint8_t *)rseq.data();
     V.b.ref_qual = fasta ? nullptr : (const uint8_t *)c.ref[3].data();
     V.b.aln_off = aln_off, V.b.pos = pos.data(), V.b.score = score.data(), V.b.has_score = has_score.data();

@@ -316,7 +316,7 @@ def hand():
 
 
 @pytest.mark.parametrize("name", ["ins_tie_rank", "skip_277", "skip_354", "skip_384", "del_ins_pair", "leading_ins",
-                                  "del_quals", "ref_alone"])
+                                  "del_quals", "ref_alone", "rev_ins_wins"])
 def test_consensus_equals_the_oracle_on_hand_cases(hand, name):
     _check_case(name, *hand[name])
 
@@ -362,6 +362,12 @@ def test_the_hand_cases_reach_what_they_are_for(hand):
     assert o["fastq"].split("\n")[1] == ref[:51] + "TT" + ref[51:]
     flipped = _oracle(ccs_cases.to_case("ins_tie_rank", ref, rq, alns[::-1]))
     assert flipped["fastq"].split("\n")[1] == ref[:51] + "TT" + ref[51:]   # seen first either way: not column order
+    # the reverse-strand subread's insertion: GT wins column 40, and its first carrier is the first alignment
+    ref, rq, alns = hand["rev_ins_wins"]
+    assert [a[4:] for a in alns] == [(1,), (), ()] and all(60 <= len(a[0]) <= 80 for a in alns)
+    o = _oracle(ccs_cases.to_case("rev_ins_wins", ref, rq, alns))
+    assert o["fastq"].split("\n")[1] == ref[:41] + "GT" + ref[41:]
+    assert _oracle(ccs_cases.to_case("rev_ins_wins", ref, rq, alns[1:]))["fastq"].split("\n")[1] == ref[:41] + "CC" + ref[41:]
 
 
 def test_leading_insertion_state_without_trimming(hand):
